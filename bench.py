@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Training throughput of the dense-correspondence hot path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W          (N > 1 without a launcher: bench.py starts the N ranks itself)
+    python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]
+                                                           (N > 1 without a launcher: bench.py starts the N ranks itself)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
@@ -15,14 +16,16 @@ over one synthetic batch already resident in HBM:
 Workload at N = 1: BASELINE.json configs[1] -- B = 4 image pairs (8 images / step), 640x480, D = 3, Resnet34_8s, 5000 match
 + 2500 masked + 2500 background non-match pixel pairs per image pair.  At N > 1: BASELINE configs[3] -- global batch
 8 N image pairs, every rank runs B = 8 pairs of its own (weak scaling, BN statistics per rank: the reference has no
-SyncBN); `value` is the whole-job images / second.  The same line carries, as `variants`, the measurements that complete
-the picture: the fp32-MFMA arithmetic and configs[3]'s per-GPU share on ONE GPU (N = 1), the fixed-global-batch-64
-strong-scaling point (N > 1), and `allreduce_ms` / `communication` (collective alone, exposed per step, RCCL rank count).
+SyncBN); `value` is the whole-job images / second.
 
-Prints ONE JSON line on rank 0 (contract in the task description) with `roofline` (dominant kernel = the gather-GEMM
-convolution, forward + dgrad: conv_gemm_hl_kernel on the wide layers and conv_gemm_f16_kernel on the others in the default
-split-fp16 arithmetic / conv_gemm_kernel with --conv-mode fp32; algorithmic FLOPs and per-launch durations from HIP events
-recorded by the engine on the launch stream; `roofline.hl_kernel` is the wide-layer kernel alone) and
+A plain run sets up, warms up, times exactly --steps steps (`ms_per_step` = the timed region / --steps) and prints ONE JSON
+line on rank 0; `--dump-outputs DIR` writes what the last timed step computed (dump_outputs) before the line.  Everything
+else needs `--full`, which adds after the headline: as `variants`, the measurements that complete the picture (the fp32-MFMA
+arithmetic and configs[3]'s per-GPU share on ONE GPU (N = 1), the fixed-global-batch-64 strong-scaling point (N > 1)),
+`allreduce_ms` / `communication` (collective alone, exposed per step, RCCL rank count), `roofline` (dominant kernel = the
+gather-GEMM convolution, forward + dgrad: conv_gemm_hl_kernel on the wide layers and conv_gemm_f16_kernel on the others in
+the default split-fp16 arithmetic / conv_gemm_kernel with --conv-mode fp32; algorithmic FLOPs and per-launch durations from
+HIP events recorded by the engine on the launch stream; `roofline.hl_kernel` is the wide-layer kernel alone) and
 `cpu_baseline` (the oracle's step on this box's host cores, bounded sample).  `--workload pairgen` measures the device
 pair generator instead.
 """
@@ -373,8 +376,9 @@ class Job(object):
         self.opt.step()
         return loss
 
-    def timed(self, warmup, steps, first_it, use_dist):
-        """W untimed steps, then exactly K steps between barrier + synchronize; max over ranks.  -> (seconds, last loss)"""
+    def timed(self, warmup, steps, first_it, use_dist, idle=True):
+        """W untimed steps, then exactly K steps between barrier + synchronize; max over ranks.  -> (seconds, last loss)
+        ``idle``: then two more steps for ``host_enqueue_idle_ms`` (idle_enqueue)."""
         loss = None
         for it in range(warmup):
             loss = self.step(first_it + it)
@@ -394,19 +398,49 @@ class Job(object):
             t = torch.tensor([elapsed], dtype=torch.float64, device=self.dev)
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
             elapsed = float(t.item())
-        # (outside the timed region) the same enqueue against an IDLE GPU, one step at a time with a synchronisation in
-        # between: the launch queue never fills, so this is the host's own cost of a step -- Python, bindings, the engine's
-        # C++ and the HIP runtime's launch path -- without the back-pressure that host_enqueue_ms includes when the GPU is
-        # the slower side.  Two steps; the smaller one.
+        if idle:
+            self.idle_enqueue(first_it + warmup + steps)
+        return elapsed, loss
+
+    def idle_enqueue(self, first_it):
+        """(outside the timed region) the same enqueue against an IDLE GPU, one step at a time with a synchronisation in
+        between: the launch queue never fills, so this is the host's own cost of a step -- Python, bindings, the engine's
+        C++ and the HIP runtime's launch path -- without the back-pressure that host_enqueue_ms includes when the GPU is
+        the slower side.  Two steps; the smaller one."""
         idle = []
         for it in range(2):
             torch.cuda.synchronize()
             t1 = time.perf_counter()
-            self.step(first_it + warmup + steps + it)
+            self.step(first_it + it)
             idle.append(1e3 * (time.perf_counter() - t1))
         torch.cuda.synchronize()
         self.host_enqueue_idle_ms = min(idle)
-        return elapsed, loss
+
+
+DUMP_SAMPLE = 1 << 20   # entries kept of each flat vector by --dump-outputs (the whole Resnet34_8s is 21.3 M floats = 85 MB)
+
+
+def dump_outputs(job, loss, out_dir):
+    """`--dump-outputs DIR`: what the last timed step handed its caller, as float32 / float64 .npy files --
+    loss.npy (the step's loss), params.npy (the parameters after the optimizer step), grads.npy (the flat gradient buffer the
+    optimizer read) and bn_buffers.npy (the batch-norm running statistics the forward pass updated).  The two large vectors are
+    a fixed sample: DUMP_SAMPLE positions drawn from a generator seeded with 0, in ascending order, the same in every run."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    with torch.no_grad():
+        params = torch.cat([p.detach().reshape(-1) for p in job.grads.params])
+        flat = job.grads.flat
+        out = {"loss": np.array([float(loss.item())], dtype=np.float64),
+               "bn_buffers": torch.cat([b.detach().reshape(-1).float() for b in job.dcn.buffers() if b.is_floating_point()])}
+        for name, vec in (("params", params), ("grads", flat)):
+            if vec.numel() > DUMP_SAMPLE:
+                pick = torch.randint(0, vec.numel(), (DUMP_SAMPLE,), generator=torch.Generator().manual_seed(0)).sort().values
+                vec = vec[pick.to(vec.device)]
+            out[name] = vec
+    for name, v in out.items():
+        if torch.is_tensor(v):
+            v = v.float().cpu().numpy()
+        np.save(os.path.join(out_dir, name + ".npy"), v)
 
 
 def main():
@@ -417,8 +451,15 @@ def main():
     ap.add_argument("--workload", default=None, choices=sorted(WORKLOADS) + ["pairgen"],
                     help="default: config2 (BASELINE configs[1]) on one GPU, config4 (configs[3]: B = 8 pairs per GPU) on several")
     ap.add_argument("--batch", type=int, default=0, help="override image pairs per GPU per step")
-    ap.add_argument("--cpu-baseline-steps", type=int, default=5, help="0 disables the CPU baseline leg")
-    ap.add_argument("--profile-steps", type=int, default=3, help="extra steps with per-launch HIP events (roofline)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also measure everything else the line can carry: the CPU baseline, the roofline "
+                         "and step-breakdown steps, the loss-gather roofline, the variants (other arithmetic, workloads and "
+                         "scaling points), the host's idle enqueue time and, with several ranks, the all-reduce alone.  Without it "
+                         "a run sets up, warms up, times --steps steps and prints the line (those fields null / empty)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/<name>.npy (see dump_outputs)")
+    ap.add_argument("--cpu-baseline-steps", type=int, default=5, help="(--full) 0 disables the CPU baseline leg")
+    ap.add_argument("--profile-steps", type=int, default=3, help="(--full) extra steps with per-launch HIP events (roofline)")
     ap.add_argument("--conv-mode", default="f16x3", choices=["f16x3", "fp32"],
                     help="convolution arithmetic (include/dcn_hip.h): split-fp16 on the fp16 MFMA pipe with fp32-level "
                          "accuracy (default), or fp32 MFMA")
@@ -435,9 +476,13 @@ def main():
     ap.add_argument("--dry-run-cpu", action="store_true",
                     help="NOT a measurement: run the bench's control flow (respawn, rendezvous, bucketed all-reduce, barriers, "
                          "scaling legs, JSON line) on CPU with host-emulated kernels and gloo -- see enter_cpu_dry_run")
-    ap.add_argument("--no-variants", action="store_true", help="skip the extra measurements (fp32-MFMA mode, config 4 on one "
-                                                                "GPU, strong-scaling point) that ride on the JSON line")
+    ap.add_argument("--no-variants", action="store_true", help="(--full) skip the extra measurements (fp32-MFMA mode, config 4 "
+                                                                "on one GPU, strong-scaling point) that ride on the JSON line")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if not args.full:
+        args.cpu_baseline_steps, args.profile_steps, args.no_variants = 0, 0, True
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         respawn_under_torchrun(args.gpus, args.dry_run_cpu)   # does not return
@@ -474,6 +519,8 @@ def main():
     if args.workload == "pairgen":
         if world > 1:
             raise SystemExit("--workload pairgen is a single-GPU measurement")
+        if args.dump_outputs:
+            raise SystemExit("--dump-outputs: the training step's outputs; --workload pairgen has none")
         return pairgen_bench(args)
     from dcn_hip import _lib, backbone as bb
     bb.set_conv_mode(args.conv_mode)
@@ -492,7 +539,11 @@ def main():
     graph_note = job.graph_note
     step = job.step
 
-    elapsed, loss = job.timed(args.warmup, args.steps, 0, use_dist)
+    elapsed, loss = job.timed(args.warmup, args.steps, 0, use_dist, idle=False)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(job, loss, args.dump_outputs)
+    if args.full:
+        job.idle_enqueue(args.warmup + args.steps)
     host_enqueue_ms = job.host_enqueue_ms
     final_loss = float(loss.item())
     # every rank's host time to enqueue a step (8 ranks share the box's usable cores: a rank whose enqueue time approaches the
@@ -507,7 +558,7 @@ def main():
     # ---- gradient all-reduce: the collective alone (whole flat buffer, RCCL), and what the step really pays for it
     # (same steps with the communication switched off; the bucketed schedule hides all but the last bucket)
     comm = None
-    if use_dist:
+    if use_dist and args.full:
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         reps = 10
         for _ in range(3):

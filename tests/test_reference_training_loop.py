@@ -1,14 +1,12 @@
-"""The drop-in claim, executed.
+"""The drop-in claim, checked without the reference's tree.
 
-* With this repository's source root in front of the reference's on ``sys.path`` the packages MERGE (dcn_hip/_dropin.py):
-  ``dense_correspondence.training.training``, the real ``SpartanDataset``, ``evaluation.evaluation``, ``utils.transformations``
-  resolve to the reference, network / loss / ``resnet_dilated`` to the MI355X path.
-* The reference's OWN driver -- ``DenseCorrespondenceTraining.run()`` + ``run_from_pretrained()``, training.py:46-601, imported
-  from /root/reference (Python-2 text converted in memory, nothing copied) -- runs against the product (kernels host-emulated
-  here) and logs the loss sequence the reference's own network / loss modules log (``tests/golden/training_loop_ref.npz``, made by
-  ``tests/golden/make_training_loop_golden_from_reference.py``), writes the same files, and its checkpoints load back.
-* Where /root/reference does not exist (the GPU box) the recorded batches are replayed through the same call sequence against
-  the fixture: on the MI355X under ``-m gpu``, host-emulated otherwise.
+* With this repository's source root in front of a second one on ``sys.path`` the packages MERGE (dcn_hip/_dropin.py): the
+  names this root does not provide resolve to the other root, network / loss / ``resnet_dilated`` to the MI355X path (checked
+  on a synthetic second source root).
+* ``tests/golden/training_loop_ref.npz`` records the loss sequence, parameter norms and files of the reference's OWN driver --
+  ``DenseCorrespondenceTraining.run()`` + ``run_from_pretrained()``, training.py:46-601 -- on a tiny in-memory dataset (made by
+  ``tests/golden/make_training_loop_golden_from_reference.py`` where the reference's tree is at hand).  The recorded batches are
+  replayed through the same call sequence against the product: on the MI355X under ``-m gpu``, host-emulated otherwise.
 """
 import os
 import subprocess
@@ -20,14 +18,11 @@ import pytest
 import torch
 
 import reference_loop_runner as runner
-import reference_py3
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 PKG = os.path.join(ROOT, "pytorch-dense-correspondence_amd")
 FIXTURE = os.path.join(HERE, "golden", "training_loop_ref.npz")
-
-needs_reference = pytest.mark.skipif(not reference_py3.available(), reason="the reference tree is not mounted on this box")
 
 
 def _python(code, *paths, env=None):
@@ -141,46 +136,7 @@ def test_placeholders_alone():
     assert r.returncode == 0 and r.stdout.strip().endswith("OK"), r.stdout + r.stderr
 
 
-# ---- the real reference tree ---------------------------------------------------------------------------------------------
-
-@needs_reference
-def test_import_probe_against_the_real_reference():
-    """The five modules VERDICT r5 probed (ModuleNotFoundError then) + where each name of training.py:20-43 comes from."""
-    r = _python("""
-        import os
-        sys.path.insert(0, %r)
-        import reference_py3 as rp
-        rp.install(); rp.install_third_party_stubs()
-        os.environ["DC_SOURCE_DIR"] = rp.REF
-        sys.path += [rp.REF, os.path.join(rp.REF, "modules")]
-        import importlib
-        theirs = ["dense_correspondence.training.training", "dense_correspondence.dataset.dense_correspondence_dataset_masked",
-                  "dense_correspondence.dataset.spartan_dataset_masked", "dense_correspondence.evaluation.evaluation",
-                  "dense_correspondence_manipulation.utils.transformations", "dense_correspondence_manipulation.utils.utils",
-                  "dense_correspondence_manipulation.utils.constants", "dense_correspondence.dataset.scene_structure",
-                  "dense_correspondence.correspondence_tools.correspondence_augmentation"]
-        ours = ["dense_correspondence.network.dense_correspondence_network", "dense_correspondence.loss_functions.loss_composer",
-                "dense_correspondence.loss_functions.pixelwise_contrastive_loss",
-                "pytorch_segmentation_detection.models.resnet_dilated", "dense_correspondence.correspondence_tools.correspondence_finder",
-                "dense_correspondence.evaluation.utils", "tensorboard_logger"]
-        for m in theirs:
-            f = importlib.import_module(m).__file__
-            assert f.startswith(rp.REF), (m, f)
-        for m in ours:
-            f = importlib.import_module(m).__file__
-            assert f.startswith(%r), (m, f)
-        import dense_correspondence.training.training as t
-        assert t.SpartanDataset.__module__ == "dense_correspondence.dataset.spartan_dataset_masked" and hasattr(t.SpartanDataset, "get_within_scene_data")
-        assert t.DenseCorrespondenceNetwork.__module__ == "dense_correspondence.network.dense_correspondence_network"
-        assert hasattr(t.DenseCorrespondenceNetwork, "forward_pair")                         # (the product's class)
-        assert t.DenseCorrespondenceEvaluation.__module__ == "dense_correspondence.evaluation.evaluation"
-        from dense_correspondence.evaluation.utils import PandaDataFrameWrapper               # evaluation.py:34, handed on
-        import dense_correspondence.correspondence_tools.correspondence_finder as cf
-        assert callable(cf.pinhole_projection_image_to_world) and cf.batch_find_pixel_correspondences.__module__ == cf.__name__
-        print("OK")
-        """ % (HERE, PKG), PKG)
-    assert r.returncode == 0 and r.stdout.strip().endswith("OK"), r.stdout + r.stderr
-
+# ---- replay of the recorded run (no reference needed; on the MI355X under -m gpu) ------------------------------------------
 
 def _assert_matches_fixture(z, g, first_tol, later_tol):
     assert list(z["served"]) == list(g["served"]) and list(z["loss_steps"]) == list(g["loss_steps"])
@@ -197,33 +153,6 @@ def _assert_matches_fixture(z, g, first_tol, later_tol):
         assert (d <= 1e-3 * np.abs(g[k]) + 2e-3).all(), (k, d.max())
     assert np.array_equal(z["heads_initial"], g["heads_initial"])
 
-
-@needs_reference
-def test_fixture_regenerates_from_the_reference(tmp_path):
-    out = str(tmp_path / "ref.npz")
-    subprocess.check_call([sys.executable, os.path.join(HERE, "reference_loop_runner.py"), "--mode", "reference", "--out", out],
-                          stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL, timeout=900)
-    z, g = np.load(out), np.load(FIXTURE)
-    for k in g.files:
-        assert np.array_equal(z[k], g[k]), k
-    assert str(z["network_file"]).startswith(reference_py3.REF) and str(z["loss_file"]).startswith(reference_py3.REF)
-
-
-@needs_reference
-def test_reference_training_driver_runs_on_the_product(tmp_path):
-    """training.py unchanged (2to3 in memory), real SpartanDataset subclass, reference's training.yaml; network + loss = product."""
-    out = str(tmp_path / "prod.npz")
-    p = subprocess.run([sys.executable, os.path.join(HERE, "reference_loop_runner.py"), "--mode", "product", "--library", "hostemu",
-                        "--out", out], capture_output=True, text=True, timeout=1800)
-    assert p.returncode == 0, p.stdout[-3000:] + p.stderr[-3000:]
-    z, g = np.load(out), np.load(FIXTURE)
-    assert str(z["training_file"]).startswith(reference_py3.REF) and str(z["dataset_file"]).startswith(reference_py3.REF)
-    assert str(z["network_file"]).startswith(PKG) and str(z["loss_file"]).startswith(PKG)
-    assert "empty data, continuing" in p.stdout                        # the loader's sentinel branch (training.py:304-306)
-    _assert_matches_fixture(z, g, 1e-4, 1e-3)
-
-
-# ---- replay of the recorded run (no reference needed; on the MI355X under -m gpu) ------------------------------------------
 
 def _replay(device, tmp_path):
     """The call sequence of training.py:228-456 + 169-226 restated (the GPU box has no reference tree to import it from):
