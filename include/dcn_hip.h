@@ -567,6 +567,48 @@ int dcn_adam_step(int n, void* const* param, const void* const* grad, void* cons
                   const int64_t* numel, double lr, double beta1, double beta2, double eps, double weight_decay,
                   int64_t step, void* stream);
 
+/* =====================================================================================================
+ * 7. Training-image augmentation -- replaces, for device-resident images, the data augmentation of every within-scene
+ *    sample (dense_correspondence/dataset/spartan_dataset_masked.py:667-680) and the ToTensor + Normalize after it
+ *    (:297-304), i.e. dense_correspondence/correspondence_tools/correspondence_augmentation.py
+ *      random_domain_randomize_background / domain_randomize_background / get_random_image (:86-215)
+ *      random_image_and_indices_mutation / flip_vertical / flip_horizontal (:19-83)
+ *    Images: uint8 [h][w][3]; masks: uint8 [h][w] with values 0 / 1 (other values follow the reference's uint8 formula
+ *    rgb*m + (1-m)*bg, which is outside the contract).  One record of DCN_AUG_PARAM_WORDS int32 per image:
+ *      [0] flags (DCN_AUG_*)   [1..3] rgb1 (solid colour / gradient start, 0..255)   [4..6] rgb2 (gradient end)
+ *      [7] 0   [8..9] 64-bit noise seed (low word, high word)   [10..15] 0
+ *    Randomization (when DCN_AUG_RANDOMIZE) runs on the unrotated image: the gradient position and the noise index of an
+ *    output pixel are those of its source pixel.  Gradient: uint8(rgb2*p + rgb1*(1.0-p)) in float64, p = linspace(0, 1, n)
+ *    along rows (DCN_AUG_VERTICAL) or columns.  Noise (DCN_AUG_NOISE): bg + d mod 256 with d = n1 - n2 mod 256, n1, n2
+ *    uniform on 0..49, read from `noise` ([images][h][w][3]) or, when noise == NULL, from a counter-based hash of
+ *    (seed, image, source pixel, channel).
+ * ===================================================================================================== */
+#define DCN_AUG_PARAM_WORDS 16
+#define DCN_AUG_FLIP_V 1
+#define DCN_AUG_FLIP_H 2
+#define DCN_AUG_RANDOMIZE 4
+#define DCN_AUG_GRADIENT 8
+#define DCN_AUG_VERTICAL 16
+#define DCN_AUG_NOISE 32
+#define DCN_UV_INT64 0
+#define DCN_UV_FLOAT32 1
+/* n image pairs (rgb_b == mask_b == NULL: n images of side a only) in ONE launch.  params: device [sides * n] records, side
+ * a's first; noise: device [sides * n][h][w][3] or NULL; mean, std: HOST float [3].  Outputs (each may be NULL):
+ *   net_*      float [n][3][h][w] = (float(x) / 255 - mean_c) / std_c, IEEE division (torch ToTensor + Normalize)
+ *   rgb_out_*  uint8 [n][h][w][3] the augmented image          mask_out_*  float [n][h][w] the (rotated) mask as 0.0 / 1.0 */
+int dcn_augment_images(int n, int h, int w, const uint8_t* rgb_a, const uint8_t* rgb_b, const uint8_t* mask_a,
+                       const uint8_t* mask_b, const int32_t* params, const uint8_t* noise, const float* mean,
+                       const float* std, float* net_a, float* net_b, uint8_t* rgb_out_a, uint8_t* rgb_out_b,
+                       float* mask_out_a, float* mask_out_b, void* stream);
+/* out[p][y][x] = in[p][flip_v ? h-1-y : y][flip_h ? w-1-x : x] for `planes` planes of pixels of 1 .. 64 bytes; out != in */
+int dcn_flip_planes(const void* in, void* out, int64_t planes, int h, int w, int bytes_per_pixel, int flip_v, int flip_h,
+                    void* stream);
+/* u -> (w-1) - u (DCN_AUG_FLIP_H), v -> (h-1) - v (DCN_AUG_FLIP_V) in the list's type (DCN_UV_*), out may equal in.
+ * offsets: device int64 [n_images + 1] (entries [offsets[b], offsets[b+1]) belong to image b; others are copied) or NULL
+ * (n_images == 1); the flags come from params[b * DCN_AUG_PARAM_WORDS] (device records) or, params == NULL, `flags`. */
+int dcn_flip_uv(int uv_dtype, const void* u_in, const void* v_in, void* u_out, void* v_out, int64_t count, int n_images,
+                const int64_t* offsets, const int32_t* params, int flags, int h, int w, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
