@@ -609,6 +609,50 @@ int dcn_flip_planes(const void* in, void* out, int64_t planes, int h, int w, int
 int dcn_flip_uv(int uv_dtype, const void* u_in, const void* v_in, void* u_out, void* v_out, int64_t count, int n_images,
                 const int64_t* offsets, const int32_t* params, int flags, int h, int w, void* stream);
 
+/* =====================================================================================================
+ * 8. Synthetic multi-object samples -- replaces, for device-resident images, the merge step of the SYNTHETIC_MULTI_OBJECT
+ *    sample (dense_correspondence/dataset/spartan_dataset_masked.py:890-960) and the ToTensor + Normalize after it, i.e.
+ *    dense_correspondence/correspondence_tools/correspondence_augmentation.py
+ *      merge_images_with_occlusions (:217-297), prune_matches_if_occluded (:300-335), merge_matches (:337-345)
+ *    Images: uint8 [n][h][w][3]; masks: uint8 [n][h][w] with values 0 / 1 (other values follow the reference's uint8
+ *    formulas, outside the contract).  Object a's and object b's images of frame 1 and frame 2.  One foreground record per
+ *    (sample, frame): foreground [n][2] int32, DCN_MERGE_FG_A or DCN_MERGE_FG_B (the reference: random.random() < 0.5 puts
+ *    object b in front).
+ * ===================================================================================================== */
+#define DCN_MERGE_FG_A 0
+#define DCN_MERGE_FG_B 1
+#define DCN_MERGE_DROP_EMPTY 1      /* dcn_merge_prune flag: a sample whose a or b list ends up empty loses all its entries */
+#define DCN_MERGE_BAD_INDEX 1       /* status bit: an entry's (u, v) was outside the image (the entry is dropped) */
+#define DCN_MERGE_BAD_OFFSETS 2     /* status bit: offsets_a / offsets_b not increasing within [0, count] (every sample empty) */
+/* n samples x `frames` (1 or 2; frame-2 pointers NULL for 1) in ONE launch.  Frame f of sample s: the foreground object's
+ * image over the other's, fg*m + bg*(1-m) per channel in uint8 arithmetic, and the merged mask clip(mask_a + mask_b, 0, 1)
+ * of their uint8 sum.  mean, std: HOST float [3].  Outputs (each may be NULL):
+ *   net_f   float [n][3][h][w] = (float(x) / 255 - mean_c) / std_c of the merged image, IEEE division (as dcn_augment_images)
+ *   mask_f  float [n][h][w] the merged mask as 0.0 / 1.0          rgb_f  uint8 [n][h][w][3] the merged image */
+int dcn_merge_images(int n, int frames, int h, int w, const int32_t* foreground, const uint8_t* rgb_a1, const uint8_t* rgb_b1,
+                     const uint8_t* rgb_a2, const uint8_t* rgb_b2, const uint8_t* mask_a1, const uint8_t* mask_b1,
+                     const uint8_t* mask_a2, const uint8_t* mask_b2, const float* mean, const float* std, float* net_1,
+                     float* net_2, float* mask_1, float* mask_2, uint8_t* rgb_1, uint8_t* rgb_2, void* stream);
+/* Occlusion prune and concatenation over n samples, two launches, no host synchronisation.  Object a's match list of sample
+ * s is entries [offsets_a[s], offsets_a[s+1]) of u_a1 / v_a1 (its pixels in frame 1) and u_a2 / v_a2 (frame 2), int64;
+ * object b's likewise (offsets_* may be NULL when count_* == 0).  Entry i of object a is kept unless, in frame 1 or frame 2,
+ * foreground puts b in front and mask_b<f>[s][v_a<f>[i]][u_a<f>[i]] != 0 (the reference prunes frame 1's background pair by
+ * its first list, then frame 2's swapped pair); the same with a and b exchanged.  A NULL mask occludes nothing, and the
+ * entries' (u, v) of a frame are range-checked exactly when the other object's mask of that frame is given: an entry outside
+ * [0, w) x [0, h) sets DCN_MERGE_BAD_INDEX in *status and is dropped, never read out of bounds.  Outputs, capacity
+ * count_a + count_b each: u_1, v_1, u_2, v_2 = for every sample in order, a's kept entries then b's (merge_matches(uv_a1,
+ * uv_b1) / (uv_a2, uv_b2)); entries [offsets[n], count_a + count_b) are -1.  offsets: int64 [n + 1], sample s at
+ * [offsets[s], offsets[s+1]); empty: uint8 [n], 1 when a's or b's kept list is empty (with DCN_MERGE_DROP_EMPTY such a
+ * sample also contributes no entry, as the reference returns an empty sample); status: int32 [1], DCN_MERGE_BAD_* bits
+ * (written, not accumulated).  workspace: device, dcn_merge_prune_workspace(n, count_a, count_b) bytes. */
+size_t dcn_merge_prune_workspace(int n, int64_t count_a, int64_t count_b);
+int dcn_merge_prune(int n, int h, int w, const int32_t* foreground, const uint8_t* mask_a1, const uint8_t* mask_b1,
+                    const uint8_t* mask_a2, const uint8_t* mask_b2, const int64_t* u_a1, const int64_t* v_a1,
+                    const int64_t* u_a2, const int64_t* v_a2, const int64_t* offsets_a, int64_t count_a, const int64_t* u_b1,
+                    const int64_t* v_b1, const int64_t* u_b2, const int64_t* v_b2, const int64_t* offsets_b, int64_t count_b,
+                    int flags, int64_t* u_1, int64_t* v_1, int64_t* u_2, int64_t* v_2, int64_t* offsets, uint8_t* empty,
+                    int32_t* status, void* workspace, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -22,6 +22,7 @@
 // not change it and the same record gives the same bits.  The mirror path passes the reference's own host-drawn noise
 // instead, as one (n1 - n2) mod 256 plane.
 #include "dcn_common.h"
+#include "image_norm.h"
 
 #pragma clang fp contract(off)   // (the build passes -ffp-contract=off as well; the gradient must not fuse into an FMA)
 
@@ -124,15 +125,6 @@ __device__ __forceinline__ void blend(const Record& r, const AugArgs& a, int sy,
     for (int c = 0; c < 3; ++c) out[c] = (src[c] * m + mc * (bg[c] & 0xffU)) & 0xffU;   // uint8 arithmetic, as numpy
 }
 
-// (c, x) -> (x / 255 - mean_c) / std_c: torch's ToTensor + Normalize, one IEEE operation at a time
-__device__ __forceinline__ void build_lut(const AugArgs& a, float (*lut)[256]) {
-    for (int k = threadIdx.x; k < 768; k += kAugThreads) {
-        const int c = k >> 8;
-        lut[c][k & 255] = ((float)(k & 255) / 255.0f - a.mean[c]) / a.std[c];
-    }
-    __syncthreads();
-}
-
 // Work-item t of workgroup x owns the 4-pixel groups x * kAugThreads * kAugGroups + t + j * kAugThreads, j < kAugGroups.  All
 // loads are issued before the table is built (its divisions and barrier hide under their latency).
 __global__ void __launch_bounds__(kAugThreads) augment_kernel(AugArgs a) {
@@ -150,7 +142,7 @@ __global__ void __launch_bounds__(kAugThreads) augment_kernel(AugArgs a) {
     float* net = a.net[side] ? a.net[side] + (size_t)i * 3 * hw : nullptr;
     const int64_t g0 = (int64_t)blockIdx.x * kAugThreads * kAugGroups + threadIdx.x;
     if (!a.vec) {   // any width / alignment: pixel by pixel
-        if (net) build_lut(a, lut);
+        if (net) dcn::build_norm_table<kAugThreads>(lut, a.mean, a.std);
         for (int g = 0; g < kAugGroups; ++g) {
             for (int j = 0; j < kAugPix; ++j) {
                 const int64_t p = (g0 + (int64_t)g * kAugThreads) * kAugPix + j;
@@ -164,11 +156,7 @@ __global__ void __launch_bounds__(kAugThreads) augment_kernel(AugArgs a) {
                 if (noise)
                     for (int c = 0; c < 3; ++c) nz[c] = noise[sp * 3 + c];
                 blend(r, a, sy, sx, src, m, noise != nullptr, nz, px);
-                for (int c = 0; c < 3; ++c) {
-                    if (rgb_out) rgb_out[p * 3 + c] = (unsigned char)px[c];
-                    if (net) net[(size_t)c * hw + p] = lut[c][px[c]];
-                }
-                if (mask_out) mask_out[p] = (float)m;
+                dcn::store_pixel(lut, p, hw, px, (float)m, net, rgb_out, mask_out);
             }
         }
         return;
@@ -202,7 +190,7 @@ __global__ void __launch_bounds__(kAugThreads) augment_kernel(AugArgs a) {
             x0s[g] = x0;
         }
     }
-    if (net) build_lut(a, lut);
+    if (net) dcn::build_norm_table<kAugThreads>(lut, a.mean, a.std);
 #pragma unroll
     for (int g = 0; g < kAugGroups; ++g) {
         if (ys[g] < 0) continue;
@@ -219,40 +207,22 @@ __global__ void __launch_bounds__(kAugThreads) augment_kernel(AugArgs a) {
             }
             ms[q] = (mw[g] >> (8 * q)) & 0xffU;
         }
-        uint32_t o[3] = {0u, 0u, 0u};
-        float nv[3][kAugPix], mv[kAugPix];
+        uint32_t px[kAugPix][3];
+        float mv[kAugPix];
 #pragma unroll
         for (int j = 0; j < kAugPix; ++j) {
             const int qf = kAugPix - 1 - j;                      // output pixel j's source within the group: qf if fh, else j
-            uint32_t src[3], nz[3], px[3];
+            uint32_t src[3], nz[3];
 #pragma unroll
             for (int c = 0; c < 3; ++c) {
                 src[c] = r.fh ? sv[qf][c] : sv[j][c];
                 nz[c] = r.fh ? nv3[qf][c] : nv3[j][c];
             }
             const uint32_t m = r.fh ? ms[qf] : ms[j];
-            blend(r, a, sy, sx0 + (r.fh ? qf : j), src, m, noise != nullptr, nz, px);
-#pragma unroll
-            for (int c = 0; c < 3; ++c) {
-                const int byte = 3 * j + c;
-                o[byte >> 2] |= px[c] << (8 * (byte & 3));
-                nv[c][j] = net ? lut[c][px[c]] : 0.f;
-            }
+            blend(r, a, sy, sx0 + (r.fh ? qf : j), src, m, noise != nullptr, nz, px[j]);
             mv[j] = (float)m;
         }
-        const int64_t op = (int64_t)y * w + x0;
-        if (rgb_out) {
-            uint32_t* d = reinterpret_cast<uint32_t*>(rgb_out + op * 3);
-            d[0] = o[0];
-            d[1] = o[1];
-            d[2] = o[2];
-        }
-        if (net) {
-#pragma unroll
-            for (int c = 0; c < 3; ++c)
-                *reinterpret_cast<float4*>(net + (size_t)c * hw + op) = make_float4(nv[c][0], nv[c][1], nv[c][2], nv[c][3]);
-        }
-        if (mask_out) *reinterpret_cast<float4*>(mask_out + op) = make_float4(mv[0], mv[1], mv[2], mv[3]);
+        dcn::store_pixels4(lut, (int64_t)y * w + x0, hw, px, mv, net, rgb_out, mask_out);
     }
 }
 

@@ -179,6 +179,10 @@ SYMBOLS = {
     "dcn_flip_planes": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_int, c_int, c_void_p]),
     "dcn_flip_uv": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_int, c_int,
                             c_int, c_void_p]),
+    "dcn_merge_images": (c_int, [c_int, c_int, c_int, c_int] + [c_void_p] * 18),
+    "dcn_merge_prune_workspace": (c_size_t, [c_int, c_int64, c_int64]),
+    "dcn_merge_prune": (c_int, [c_int, c_int, c_int] + [c_void_p] * 10 + [c_int64] + [c_void_p] * 5 + [c_int64, c_int]
+                        + [c_void_p] * 9),
 }
 
 ERRORS = {-1: "DCN_E_INVALID (bad argument)", -2: "DCN_E_LAUNCH (kernel launch failed)",

@@ -10,9 +10,14 @@ within-scene sample goes through (``spartan_dataset_masked.py:667-680``), same n
   outside the contract).
 * PIL images and numpy arrays -- the reference's CPU loader -- go unchanged to the reference's own module (behind this source
   root, dcn_hip/_dropin.py), and raise with the reason when it does not import.
-* Every other name (``get_random_image``, ``merge_images_with_occlusions`` ...) is handed on to the reference's module.
+* ``merge_images_with_occlusions``, ``prune_matches_if_occluded`` and ``merge_matches`` (the SYNTHETIC_MULTI_OBJECT sample,
+  ``spartan_dataset_masked.py:890-960``) take image tensors the same way (csrc/merge_kernels.hip): one ``random.random()`` per
+  merge, a uint8 tensor where the reference returns a PIL image or a numpy array, ``(None, None)`` when every match is
+  occluded (one host read of the kept count), ``IndexError`` for a match outside the image.
+* Every other name (``get_random_image`` ...) is handed on to the reference's module.
 
-The batched path that writes the network's inputs for a whole batch in one launch is ``dcn_hip.augment.augment_image_pairs``.
+The batched paths that write the network's inputs for a whole batch in one launch are ``dcn_hip.augment.augment_image_pairs``
+and ``dcn_hip.merge.merge_synthetic_samples``.
 """
 import random
 
@@ -20,6 +25,7 @@ import numpy as np
 import torch
 
 from dcn_hip import augment as _aug
+from dcn_hip import merge as _merge
 from dcn_hip._dropin import reference_sibling as _reference_sibling
 
 _ref = _reference_sibling(__name__, __file__)
@@ -122,3 +128,64 @@ def domain_randomize_background(image_rgb, image_mask):
     out = _aug.augment_images(image_rgb.view(1, h, w, 3), mask.to(dev).reshape(1, h, w),
                               torch.from_numpy(rec).to(dev), noise=noise, want_input=False, want_rgb=True, want_mask=False)
     return out["rgb_a"][0]
+
+
+def merge_images_with_occlusions(image_a, image_b, mask_a, mask_b, matches_pair_a, matches_pair_b):
+    """:217-297.  One ``random.random()``: below 1/2 object b is in front, otherwise a.  uint8 [H, W, 3] images and 0/1 [H, W]
+    masks in; -> (merged uint8 [H, W, 3], merged mask uint8 [H, W] = clip(mask_a + mask_b, 0, 1), matches_a,
+    associated_matches_a, matches_b, associated_matches_b): the front object's pair as given, the other's pruned by the front
+    mask (``(None, None)`` when nothing stays)."""
+    if not torch.is_tensor(image_a):
+        return _reference("merge_images_with_occlusions")(image_a, image_b, mask_a, mask_b, matches_pair_a, matches_pair_b)
+    front_b = random.random() < 0.5
+    if image_a.dim() != 3 or image_a.shape[2] != 3 or image_a.dtype != torch.uint8:
+        raise ValueError("images must be uint8 [H, W, 3] tensors, got %s %s" % (image_a.dtype, tuple(image_a.shape)))
+    h, w = int(image_a.shape[0]), int(image_a.shape[1])
+    dev = image_a.device
+    masks = [(m if torch.is_tensor(m) else torch.as_tensor(np.asarray(m))).to(dev).reshape(1, h, w) for m in (mask_a, mask_b)]
+    fg = torch.tensor([[_merge.FG_B if front_b else _merge.FG_A, _merge.FG_A]], dtype=torch.int32).to(dev)
+    out = _merge.merge_images([image_a.reshape(1, h, w, 3)], [image_b.reshape(1, h, w, 3)], [masks[0]], [masks[1]], fg,
+                              frames=1, want_input=False, want_rgb=True)
+    merged_mask = out["mask"][0][0].to(torch.uint8)
+    if front_b:
+        back = prune_matches_if_occluded(masks[1][0], matches_pair_a)
+        pair_a, pair_b = back, matches_pair_b
+    else:
+        back = prune_matches_if_occluded(masks[0][0], matches_pair_b)
+        pair_a, pair_b = matches_pair_a, back
+    return out["rgb"][0][0], merged_mask, pair_a[0], pair_a[1], pair_b[0], pair_b[1]
+
+
+def prune_matches_if_occluded(foreground_mask_numpy, background_matches_pair):
+    """:300-335.  Entry i of both lists of the pair stays when ``foreground_mask[v_i, u_i] == 0`` for the FIRST list's (u, v);
+    order is kept.  int64 lists; ``(None, None)`` when nothing stays (one host read), IndexError for an entry of the first list
+    outside the mask (negative ones included: numpy would wrap them)."""
+    if not torch.is_tensor(foreground_mask_numpy):
+        return _reference("prune_matches_if_occluded")(foreground_mask_numpy, background_matches_pair)
+    mask = foreground_mask_numpy
+    if mask.dim() != 2:
+        raise ValueError("the foreground mask must be [H, W], got %s" % (tuple(mask.shape),))
+    h, w = int(mask.shape[0]), int(mask.shape[1])
+    dev = mask.device
+    first, second = background_matches_pair
+    n = int(first[0].numel())
+    mask = (mask if mask.dtype == torch.uint8 else mask.to(torch.uint8)).contiguous().view(1, h, w)
+    none = torch.empty(0, dtype=torch.int64, device=dev)
+    fg = torch.tensor([[_merge.FG_B, _merge.FG_A]], dtype=torch.int32).to(dev)
+    off = torch.tensor([0, n], dtype=torch.int64).to(dev)
+    uv_1, uv_2, offsets, _, status = _merge.prune_and_concat(h, w, fg, (first, second, off, n),
+                                                             ((none, none), (none, none), None, 0), {(1, "b"): mask},
+                                                             drop_empty=False)
+    kept, bad = (int(x) for x in torch.cat([offsets[1:], status.to(torch.int64)]).cpu())
+    if bad & _merge.BAD_INDEX:
+        raise IndexError("prune_matches_if_occluded: a match lies outside the %d x %d mask" % (h, w))
+    if kept == 0:
+        return (None, None)
+    return ((uv_1[0][:kept], uv_1[1][:kept]), (uv_2[0][:kept], uv_2[1][:kept]))
+
+
+def merge_matches(matches_one, matches_two):
+    """:337-345.  (cat(u_one, u_two), cat(v_one, v_two)) -- the reference's own torch.cat, on the tensors' device."""
+    if not (_tensors(matches_one) and _tensors(matches_two)):
+        return _reference("merge_matches")(matches_one, matches_two)
+    return (torch.cat((matches_one[0], matches_two[0])), torch.cat((matches_one[1], matches_two[1])))
