@@ -653,6 +653,74 @@ int dcn_merge_prune(int n, int h, int w, const int32_t* foreground, const uint8_
                     int flags, int64_t* u_1, int64_t* v_1, int64_t* u_2, int64_t* v_2, int64_t* offsets, uint8_t* empty,
                     int32_t* status, void* workspace, void* stream);
 
+/* =====================================================================================================
+ * 9. Training samples -- replaces, for device-resident frames, the sample recipe of the reference's loader
+ *    (dense_correspondence/dataset/spartan_dataset_masked.py): get_within_scene_data (:577-839, SINGLE_OBJECT_WITHIN_SCENE
+ *    and MULTI_OBJECT), get_across_scene_data (:1056-1141, SINGLE_OBJECT_ACROSS_SCENE and DIFFERENT_OBJECT), and the
+ *    non-match / blind-set steps of any match lists (complete_samples, e.g. after dcn_merge_prune).
+ *    n pairs of [h][w] frames: depth uint16 millimetres, masks uint8 with values 0 / 1 (the blind set is computed as
+ *    (mask != 0) != matched and 1 - mask b as mask == 0: other values are outside the contract), one 180-degree rotation
+ *    record per image, aug_params [2n][DCN_AUG_PARAM_WORDS] (section 7; a's records first; only the flip bits are read;
+ *    NULL: no rotation).  cams: device float [n][DCN_SAMPLE_CAM_FLOATS] = K (3x3), K^-1, pose a (4x4 camera-to-world),
+ *    pose b^-1 (world-to-camera), row-major, fp32.  Outputs, all on the device, no host synchronisation:
+ *      idx_a, idx_b  int64 [capacity], 16-byte aligned: for every pair p in order its lists t = 0 match, 1 masked, 2 background, 3 blind at
+ *                    [offsets[4p+t], offsets[4p+t+1]) as flattened pixels v * w + u; entries [offsets[4n], capacity) are -1
+ *      offsets int64 [4n + 1]; empty uint8 [n]; type int32 [n] = data_type, or -1 for an empty pair (its lists are empty,
+ *      as return_empty_data); status int32 [1], DCN_SAMPLE_BAD_* bits (written, not accumulated).
+ *    Within-scene recipe per pair: A = attempts candidates, drawn from mask a's pixels (list[floor(r * count)], flag
+ *    DCN_SAMPLE_ONLY_OFF_MASK; an empty mask a gives an empty pair) or uniformly ((floor(r0 * w), floor(r1 * h))); the
+ *    reprojection / occlusion test of dcn_find_correspondences; the M survivors in candidate order, rotated by the pair's
+ *    records (b's float coordinates as (w-1) - u, then truncated like `.long()`).  M == 0: empty pair.  Then, on the
+ *    rotated masks: masked = match a repeated k_masked times in a row, b from mask b's pixels (uniform over the image if mask
+ *    b is empty); background likewise with k_background from 1 - mask b (DCN_SAMPLE_MASK_INV) or uniform; blind = the
+ *    pixels where (mask a != 0) != matched, in order, b from mask b's pixels -- empty when there are none or mask b is empty.
+ *    Across-scene recipe: num_samples pixels of mask a's and of mask b's list (unrotated), each then rotated by its image's
+ *    record, into the blind slot; the other lists are empty; the pair is empty when either mask is.
+ *    Random numbers: seeds != NULL: seeds [n] int64 per pair; uniform k of site s is a counter-based hash of
+ *    (seed, s, k) on torch.rand's grid (multiples of 2^-24).  seeds == NULL (replay): rand float32 holds the caller's values,
+ *    site s of pair p at rand[rand_offsets[s * (n + 1) + p] ...  rand_offsets[s * (n + 1) + p + 1]) -- the reference's own
+ *    torch.rand streams.  Sites (DCN_SAMPLE_SITE_*) and the values each reads: CAND A (from mask a) or 2A (uniform: all u
+ *    values, then all v values, as torch.rand(2, A)); MASKED k_masked * M, or 2 k_masked * M when uniform; BACKGROUND
+ *    likewise with k_background; BLIND nb (the blind set's size); ACROSS_A, ACROSS_B num_samples each.  A stream shorter
+ *    than its site needs reads 0 there and raises DCN_SAMPLE_BAD_DRAWS.
+ * ===================================================================================================== */
+#define DCN_SAMPLE_CAM_FLOATS 50
+#define DCN_SAMPLE_SITES 6
+#define DCN_SAMPLE_SITE_CAND 0
+#define DCN_SAMPLE_SITE_MASKED 1
+#define DCN_SAMPLE_SITE_BACKGROUND 2
+#define DCN_SAMPLE_SITE_BLIND 3
+#define DCN_SAMPLE_SITE_ACROSS_A 4
+#define DCN_SAMPLE_SITE_ACROSS_B 5
+#define DCN_SAMPLE_ONLY_OFF_MASK 1  /* flag: candidates from mask a's pixels (sample_matches_only_off_mask) */
+#define DCN_SAMPLE_MASK_INV 2       /* flag: background non-matches from 1 - mask b (use_image_b_mask_inv) */
+#define DCN_SAMPLE_BAD_INDEX 1      /* status: a complete_samples entry outside the image (kept, as pixel 0) */
+#define DCN_SAMPLE_BAD_DRAWS 2      /* status: a replay stream shorter than its site needs */
+#define DCN_SAMPLE_BAD_OFFSETS 4    /* status: complete_samples offsets not increasing within [0, count] (pair empty) */
+/* device workspace bytes: within-scene (attempts, attempts); complete_samples (0, count); across-scene (0, 0) */
+size_t dcn_sample_workspace(int n, int h, int w, int64_t attempts, int64_t match_slots);
+/* capacity = n * (attempts * (1 + k_masked + k_background) + h * w); 1 <= n <= 1024 */
+int dcn_within_scene_samples(int n, int h, int w, const uint16_t* depth_a, const uint16_t* depth_b, const uint8_t* mask_a,
+                             const uint8_t* mask_b, const float* cams, int64_t attempts, int k_masked, int k_background,
+                             int flags, const int32_t* aug_params, const int64_t* seeds, const float* rand,
+                             const int64_t* rand_offsets, int data_type, int64_t* idx_a, int64_t* idx_b, int64_t capacity,
+                             int64_t* offsets, uint8_t* empty, int32_t* type, int32_t* status, void* workspace, void* stream);
+/* Matches found elsewhere: pair p's are entries [list_offsets[p], list_offsets[p+1]) of u_a / v_a (int64) and u_b / v_b
+ * (DCN_UV_INT64 or DCN_UV_FLOAT32, truncated like `.long()`), pixels of the frames BEFORE the aug_params rotation (NULL
+ * aug_params: the lists and masks are final).  A pair without matches is empty.  Flags: DCN_SAMPLE_MASK_INV only.
+ * capacity = count * (1 + k_masked + k_background) + n * h * w */
+int dcn_complete_samples(int n, int h, int w, const int64_t* u_a, const int64_t* v_a, const void* u_b, const void* v_b,
+                         int uv_b_dtype, const int64_t* list_offsets, int64_t count, const uint8_t* mask_a,
+                         const uint8_t* mask_b, int k_masked, int k_background, int flags, const int32_t* aug_params,
+                         const int64_t* seeds, const float* rand, const int64_t* rand_offsets, int data_type, int64_t* idx_a,
+                         int64_t* idx_b, int64_t capacity, int64_t* offsets, uint8_t* empty, int32_t* type, int32_t* status,
+                         void* workspace, void* stream);
+/* capacity = n * num_samples */
+int dcn_across_scene_samples(int n, int h, int w, const uint8_t* mask_a, const uint8_t* mask_b, int64_t num_samples,
+                             const int32_t* aug_params, const int64_t* seeds, const float* rand, const int64_t* rand_offsets,
+                             int data_type, int64_t* idx_a, int64_t* idx_b, int64_t capacity, int64_t* offsets, uint8_t* empty,
+                             int32_t* type, int32_t* status, void* workspace, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

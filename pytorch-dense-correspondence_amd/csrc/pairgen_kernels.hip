@@ -10,6 +10,7 @@
 // All float math is fp32 in the reference's evaluation order (mm rows as a0*x0 + a1*x1 + a2*x2 [+ a3]); HBM/latency
 // bound and tiny next to the network: 10 000 candidates + 1.5 M non-match samples per image pair.
 #include "dcn_common.h"
+#include "pairgen_project.h"
 
 namespace {
 
@@ -17,41 +18,14 @@ struct Cameras {
     float K[9], Kinv[9], Ta[16], Tbinv[16];
 };
 
-__device__ __forceinline__ float row3(const float* m, float x, float y, float z) { return m[0] * x + m[1] * y + m[2] * z; }
-__device__ __forceinline__ float row4(const float* m, float x, float y, float z) {
-    return m[0] * x + m[1] * y + m[2] * z + m[3] * 1.f;
-}
-
 __global__ void __launch_bounds__(256)
 project_kernel(const unsigned short* __restrict__ depth_a, const unsigned short* __restrict__ depth_b, int h, int w,
                Cameras cam, const int64_t* __restrict__ cand_u, const int64_t* __restrict__ cand_v, int64_t n,
                unsigned char* __restrict__ flag, float* __restrict__ u2o, float* __restrict__ v2o) {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
-    const int64_t u = cand_u[i], v = cand_v[i];
-    unsigned char ok = 0;
-    float u2 = 0.f, v2 = 0.f;
-    if (u >= 0 && u < w && v >= 0 && v < h) {
-        const float d = (float)depth_a[v * w + u] * 1.0f / 1000.0f;
-        if (d != 0.f) {
-            const float fx = (float)u * d, fy = (float)v * d, fz = d;
-            const float cx = row3(cam.Kinv, fx, fy, fz), cy = row3(cam.Kinv + 3, fx, fy, fz), cz = row3(cam.Kinv + 6, fx, fy, fz);
-            const float wx = row4(cam.Ta, cx, cy, cz), wy = row4(cam.Ta + 4, cx, cy, cz), wz = row4(cam.Ta + 8, cx, cy, cz);
-            const float bx = row4(cam.Tbinv, wx, wy, wz), by = row4(cam.Tbinv + 4, wx, wy, wz), bz = row4(cam.Tbinv + 8, wx, wy, wz);
-            const float px = row3(cam.K, bx, by, bz), py = row3(cam.K + 3, bx, by, bz), pz = row3(cam.K + 6, bx, by, bz);
-            u2 = px / pz;
-            v2 = py / pz;
-            const float ub = (float)w * 1.0f - 1e-3f, vb = (float)h * 1.0f - 1e-3f;
-            // (u2 != 0) & in range, written so that NaN coordinates are rejected
-            if (u2 > 0.f && u2 <= ub && v2 > 0.f && v2 <= vb) {
-                const int64_t fb = (int64_t)v2 * w + (int64_t)u2;            // truncation, as `.type(LongTensor)`
-                const float d2 = (float)depth_b[fb] * 1.0f / 1000.f;
-                const float z2 = pz - 0.003f;
-                ok = (d2 > 0.f && !(d2 < z2)) ? 1 : 0;
-            }
-        }
-    }
-    flag[i] = ok;
+    float u2, v2;
+    flag[i] = dcn::project_candidate(depth_a, depth_b, h, w, cam.K, cam.Kinv, cam.Ta, cam.Tbinv, cand_u[i], cand_v[i], u2, v2);
     u2o[i] = u2;
     v2o[i] = v2;
 }

@@ -181,6 +181,14 @@ SYMBOLS = {
                             c_int, c_void_p]),
     "dcn_merge_images": (c_int, [c_int, c_int, c_int, c_int] + [c_void_p] * 18),
     "dcn_merge_prune_workspace": (c_size_t, [c_int, c_int64, c_int64]),
+    "dcn_sample_workspace": (c_size_t, [c_int, c_int, c_int, c_int64, c_int64]),
+    "dcn_within_scene_samples": (c_int, [c_int, c_int, c_int] + [c_void_p] * 5 + [c_int64, c_int, c_int, c_int]
+                                 + [c_void_p] * 4 + [c_int, c_void_p, c_void_p, c_int64] + [c_void_p] * 6),
+    "dcn_complete_samples": (c_int, [c_int, c_int, c_int] + [c_void_p] * 4 + [c_int, c_void_p, c_int64, c_void_p, c_void_p,
+                                                                              c_int, c_int, c_int] + [c_void_p] * 4
+                             + [c_int, c_void_p, c_void_p, c_int64] + [c_void_p] * 6),
+    "dcn_across_scene_samples": (c_int, [c_int, c_int, c_int, c_void_p, c_void_p, c_int64] + [c_void_p] * 4
+                                 + [c_int, c_void_p, c_void_p, c_int64] + [c_void_p] * 6),
     "dcn_merge_prune": (c_int, [c_int, c_int, c_int] + [c_void_p] * 10 + [c_int64] + [c_void_p] * 5 + [c_int64, c_int]
                         + [c_void_p] * 9),
 }

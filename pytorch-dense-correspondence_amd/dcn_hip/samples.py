@@ -1,0 +1,291 @@
+"""Host side of the sample kernels (csrc/sample_kernels.hip): the training samples of the reference's loader
+(dense_correspondence/dataset/spartan_dataset_masked.py get_within_scene_data :577-839, get_across_scene_data :1056-1141) for a
+batch of device-resident frames, as the loss's concatenated pair lists.
+
+Within-scene (SINGLE_OBJECT_WITHIN_SCENE, MULTI_OBJECT), per pair: ``num_matching_attempts`` candidates (from mask a, or
+uniform), the reprojection test of ``batch_find_pixel_correspondences`` on the unaugmented frames, then the augmentation
+(``augment.augment_image_pairs``' records: background randomization of the images, 180-degree rotation of images, masks and
+matches), then on the rotated masks the masked / background non-matches (``create_non_correspondences`` +
+``create_non_matches``) and the blind non-matches.  A pair whose mask a is empty (with ``sample_matches_only_off_mask``) or
+where no match survives is empty: type -1 and no entries, as ``return_empty_data``.  Across-scene (SINGLE_OBJECT_ACROSS_SCENE,
+DIFFERENT_OBJECT): ``cross_scene_num_samples`` pixels of each mask, rotated, in the blind slot.
+
+Masks are 0/1 (uint8, or anything ``.to(uint8)`` maps onto 0/1); other values are outside the contract (include/dcn_hip.h
+section 9).  Random numbers are drawn with the caller's generator into per-pair 64-bit seeds (the kernels hash them), or the
+reference's own ``torch.rand`` streams are replayed (``draws``).  Nothing here waits for the device, except
+``SampleBatch.pair_lists()`` (one read of the offsets).
+"""
+import collections
+
+import numpy as np
+import torch
+
+from . import _lib
+from . import augment as _aug
+from .pairgen import invert_rigid
+
+ONLY_OFF_MASK, MASK_INV = 1, 2
+BAD_INDEX, BAD_DRAWS, BAD_OFFSETS = 1, 2, 4
+SITES = ("cand", "masked", "background", "blind", "across_a", "across_b")
+CAM_FLOATS = 50
+SINGLE_OBJECT_WITHIN_SCENE, SINGLE_OBJECT_ACROSS_SCENE, DIFFERENT_OBJECT, MULTI_OBJECT, SYNTHETIC_MULTI_OBJECT = 0, 1, 2, 3, 4
+
+SampleOptions = collections.namedtuple(
+    "SampleOptions", "num_matching_attempts sample_matches_only_off_mask num_masked_non_matches_per_match "
+                     "num_background_non_matches_per_match use_image_b_mask_inv cross_scene_num_samples domain_randomize")
+
+
+class SampleBatch(collections.namedtuple(
+        "SampleBatch", "input_a input_b idx_a idx_b offsets empty type status seeds aug_params mask_a mask_b")):
+    """input_a / input_b: float [B, 3, H, W] network inputs (None without RGB); idx_a / idx_b: int64 [capacity] device lists,
+    pair p's list t (match, masked, background, blind) at ``offsets[4p+t]:offsets[4p+t+1]``, -1 after ``offsets[4B]``;
+    offsets int64 [4B + 1]; empty bool [B]; type int32 [B] (data type, -1 for an empty pair); status int32 [1] (BAD_* bits);
+    seeds int64 [B] (None when replayed); aug_params int32 [2B, 16]; mask_a / mask_b: the rotated masks, float 0/1
+    [B, H, W] (None without RGB)."""
+
+    def pair_lists(self):
+        """A ``dcn_hip.loss.PairLists`` over ``idx_a`` / ``idx_b`` (no copy of the lists).  The loss API takes host offsets:
+        this reads the 4B + 1 offsets once, the only host synchronization of the sample path."""
+        from .loss import PairLists
+        return PairLists(self.idx_a, self.idx_b, self.offsets.cpu().tolist())
+
+
+def options_from_config(training_config):
+    """The sample settings of a training.yaml dict (its ``training`` section, or the whole config), with the reference's
+    ``int(fraction * n)`` rounding (dense_correspondence_dataset_masked.py:537-549)."""
+    t = training_config.get("training", training_config)
+    n = t["num_non_matches_per_match"]
+    return SampleOptions(int(t["num_matching_attempts"]), bool(t["sample_matches_only_off_mask"]),
+                         int(t["fraction_masked_non_matches"] * n), int(t["fraction_background_non_matches"] * n),
+                         bool(t["use_image_b_mask_inv"]), int(t["cross_scene_num_samples"]), bool(t["domain_randomize"]))
+
+
+def _mask(m, n, h, w, what):
+    if tuple(m.shape) != (n, h, w):
+        raise ValueError("%s must be [%d, %d, %d], got %s" % (what, n, h, w, tuple(m.shape)))
+    return (m if m.dtype == torch.uint8 else m.to(torch.uint8)).contiguous()
+
+
+def _depth(d, n, h, w, what):
+    if tuple(d.shape) != (n, h, w) or d.element_size() != 2 or d.is_floating_point():
+        raise ValueError("%s must be 16-bit integer [%d, %d, %d] millimetres, got %s %s" % (what, n, h, w, d.dtype,
+                                                                                            tuple(d.shape)))
+    return d.contiguous()
+
+
+def _f32(a):
+    return np.asarray(a, dtype=np.float64).astype(np.float32)
+
+
+def _cameras(K, pose_a, pose_b, n, dev):
+    """[n, CAM_FLOATS] fp32 (K, K^-1, pose a, pose b^-1) on ``dev`` in one copy, as pairgen.find_correspondences builds them."""
+    if K is None:
+        from dense_correspondence.correspondence_tools.correspondence_finder import get_default_K_matrix
+        K = get_default_K_matrix()
+    K = np.asarray(K.cpu() if torch.is_tensor(K) else K, dtype=np.float64)
+    Ks = np.broadcast_to(K, (n, 3, 3)) if K.shape == (3, 3) else K
+    if Ks.shape != (n, 3, 3):
+        raise ValueError("K must be [3, 3] or [%d, 3, 3], got %s" % (n, K.shape))
+    rows = [np.concatenate([_f32(k).reshape(-1), _f32(np.linalg.inv(k)).reshape(-1)]) for k in Ks]
+    rows = torch.from_numpy(np.stack(rows))
+    poses = []
+    for p, what in ((pose_a, "pose_a"), (pose_b, "pose_b")):
+        if tuple(p.shape) != (n, 4, 4):
+            raise ValueError("%s must be [%d, 4, 4], got %s" % (what, n, tuple(p.shape)))
+        poses.append(p)
+    if all(not torch.is_tensor(p) or p.device.type == "cpu" for p in poses):
+        pa = np.asarray(poses[0].numpy() if torch.is_tensor(poses[0]) else poses[0], dtype=np.float64)
+        pb = np.asarray(poses[1].numpy() if torch.is_tensor(poses[1]) else poses[1], dtype=np.float64)
+        t = np.concatenate([rows.numpy(), _f32(pa).reshape(n, 16), np.stack([_f32(invert_rigid(x)).reshape(16) for x in pb])],
+                           axis=1)
+        host = torch.from_numpy(np.ascontiguousarray(t))
+        if dev.type == "cuda":
+            host = host.pin_memory()
+        return host.to(dev, non_blocking=True)
+    # device poses: the rigid inverse in float64 on the device (no host round trip)
+    pa = torch.as_tensor(poses[0], device=dev).double()
+    pb = torch.as_tensor(poses[1], device=dev).double()
+    R = pb[:, :3, :3].transpose(1, 2)
+    inv = torch.zeros_like(pb)
+    inv[:, :3, :3] = R
+    inv[:, :3, 3] = -(R @ pb[:, :3, 3:4]).squeeze(2)
+    inv[:, 3, 3] = 1.0
+    k = rows.to(dev, non_blocking=True)
+    return torch.cat([k, pa.float().reshape(n, 16), inv.float().reshape(n, 16)], dim=1).contiguous()
+
+
+def draw_seeds(num_pairs, device, generator=None):
+    """[num_pairs] int64 seeds on ``device`` (two int32 draws each), no host sync."""
+    return torch.randint(-2 ** 31, 2 ** 31, (num_pairs, 2), device=device, generator=generator,
+                         dtype=torch.int32).view(torch.int64).view(-1)
+
+
+def pack_draws(draws, n, dev):
+    """``draws``: {site: sequence of B 1-D float arrays / tensors (None = no values)} -> (rand float32, rand_offsets int64
+    [SITES][B + 1]) on ``dev``: the replay layout of include/dcn_hip.h section 9."""
+    vals, offs, pos = [], [], 0
+    for site in SITES:
+        per = draws.get(site) or [None] * n
+        if len(per) != n:
+            raise ValueError("draws[%r] needs one entry per pair (%d), got %d" % (site, n, len(per)))
+        row = [pos]
+        for x in per:
+            a = np.zeros(0, np.float32) if x is None else np.asarray(x.cpu() if torch.is_tensor(x) else x,
+                                                                      dtype=np.float32).reshape(-1)
+            vals.append(a)
+            pos += a.size
+            row.append(pos)
+        offs.append(row)
+    unknown = set(draws) - set(SITES)
+    if unknown:
+        raise ValueError("unknown draw sites %s (sites: %s)" % (sorted(unknown), SITES))
+    rand = torch.from_numpy(np.concatenate(vals + [np.zeros(1, np.float32)]))
+    return rand.to(dev), torch.tensor(offs, dtype=torch.int64).to(dev)
+
+
+def _random(n, dev, generator, draws, seeds):
+    if draws is not None:
+        rand, roff = pack_draws(draws, n, dev)
+        return None, rand, roff
+    if seeds is None:
+        seeds = draw_seeds(n, dev, generator)
+    else:
+        seeds = torch.as_tensor(seeds).to(device=dev, dtype=torch.int64).contiguous().view(-1)
+        if seeds.numel() != n:
+            raise ValueError("seeds must hold one int64 per pair (%d)" % n)
+    return seeds, None, None
+
+
+def _params(aug_params, n, dev, generator, domain_randomize, flip):
+    if aug_params is None:
+        return _aug.draw_params(2 * n, dev, generator=generator, domain_randomize=domain_randomize, flip=flip)
+    p = torch.as_tensor(aug_params).to(device=dev, dtype=torch.int32).contiguous()
+    if tuple(p.shape) != (2 * n, _aug.PARAM_WORDS):
+        raise ValueError("aug_params must be int32 [%d, %d], got %s" % (2 * n, _aug.PARAM_WORDS, tuple(p.shape)))
+    return p
+
+
+def _outputs(n, cap, dev):
+    return (torch.empty(max(cap, 1), dtype=torch.int64, device=dev)[:cap], torch.empty(max(cap, 1), dtype=torch.int64,
+                                                                                       device=dev)[:cap],
+            torch.empty(4 * n + 1, dtype=torch.int64, device=dev), torch.empty(n, dtype=torch.bool, device=dev),
+            torch.empty(n, dtype=torch.int32, device=dev), torch.empty(1, dtype=torch.int32, device=dev))
+
+
+def _images(rgb_a, rgb_b, mask_a, mask_b, params, mean, std):
+    if rgb_a is None and rgb_b is None:
+        return None, None, None, None
+    if rgb_a is None or rgb_b is None:
+        raise ValueError("rgb_a and rgb_b go together")
+    out = _aug.augment_images(rgb_a, mask_a, params, rgb_b=rgb_b, mask_b=mask_b, mean=mean, std=std)
+    return out["input_a"], out["input_b"], out["mask_a"], out["mask_b"]
+
+
+def build_within_scene_samples(depth_a, depth_b, mask_a, mask_b, pose_a, pose_b, K=None, rgb_a=None, rgb_b=None, *,
+                               num_matching_attempts, sample_matches_only_off_mask, num_masked_non_matches_per_match,
+                               num_background_non_matches_per_match, use_image_b_mask_inv, domain_randomize=False, flip=True,
+                               mean=_aug.DEFAULT_IMAGE_MEAN, std=_aug.DEFAULT_IMAGE_STD_DEV, generator=None, draws=None,
+                               aug_params=None, seeds=None, data_type=SINGLE_OBJECT_WITHIN_SCENE):
+    """B within-scene samples on the device (get_within_scene_data).
+
+    depth_a, depth_b: 16-bit [B, H, W] millimetres (int16 / uint16, same bits); mask_a, mask_b: 0/1 [B, H, W]; pose_a, pose_b:
+    [B, 4, 4] camera-to-world (host or device); K: [3, 3] or [B, 3, 3] on the host (None: the reference's default K);
+    rgb_a, rgb_b: optional uint8 [B, H, W, 3] -> normalized network inputs of the augmented images.  ``aug_params``: [2B, 16]
+    augmentation records (augment.draw_params layout) to replay, otherwise drawn with ``generator`` (``domain_randomize``,
+    ``flip``).  ``draws``: the reference's torch.rand streams per site and pair (replay; see pack_draws), otherwise per-pair
+    ``seeds`` (drawn with ``generator`` when None).
+
+    -> SampleBatch.  Launches: the sample chain (about ten small kernels) and, with RGB, one augmentation launch; no host
+    synchronization."""
+    n, h, w = int(mask_a.shape[0]), int(mask_a.shape[1]), int(mask_a.shape[2])
+    dev = mask_a.device
+    lib = _lib.get()
+    da, db = _depth(depth_a, n, h, w, "depth_a"), _depth(depth_b, n, h, w, "depth_b")
+    ma, mb = _mask(mask_a, n, h, w, "mask_a"), _mask(mask_b, n, h, w, "mask_b")
+    A, k1, k2 = int(num_matching_attempts), int(num_masked_non_matches_per_match), int(num_background_non_matches_per_match)
+    if A < 1 or k1 < 1 or k2 < 1:
+        raise ValueError("num_matching_attempts and the non-matches per match must be >= 1")
+    params = _params(aug_params, n, dev, generator, domain_randomize, flip)
+    sd, rand, roff = _random(n, dev, generator, draws, seeds)
+    cams = _cameras(K, pose_a, pose_b, n, dev)
+    _lib.require_device(da, db, ma, mb, cams, params, sd, rand, roff)
+    cap = n * (A * (1 + k1 + k2) + h * w)
+    idx_a, idx_b, offsets, empty, typ, status = _outputs(n, cap, dev)
+    ws = torch.empty(int(lib.dcn_sample_workspace(n, h, w, A, A)), dtype=torch.uint8, device=dev)
+    flags = (ONLY_OFF_MASK if sample_matches_only_off_mask else 0) | (MASK_INV if use_image_b_mask_inv else 0)
+    P = _lib.ptr
+    rc = lib.dcn_within_scene_samples(n, h, w, P(da), P(db), P(ma), P(mb), P(cams), A, k1, k2, flags, P(params), P(sd),
+                                      P(rand), P(roff), int(data_type), P(idx_a), P(idx_b), cap, P(offsets), P(empty),
+                                      P(typ), P(status), P(ws), _lib.stream_ptr())
+    _lib.check(rc, "dcn_within_scene_samples")
+    ia, ib, mka, mkb = _images(rgb_a, rgb_b, ma, mb, params, mean, std)
+    return SampleBatch(ia, ib, idx_a, idx_b, offsets, empty, typ, status, sd, params, mka, mkb)
+
+
+def build_across_scene_samples(mask_a, mask_b, rgb_a=None, rgb_b=None, *, num_samples, domain_randomize=False, flip=True,
+                               mean=_aug.DEFAULT_IMAGE_MEAN, std=_aug.DEFAULT_IMAGE_STD_DEV, generator=None, draws=None,
+                               aug_params=None, seeds=None, data_type=SINGLE_OBJECT_ACROSS_SCENE):
+    """B across-scene / different-object samples on the device (get_across_scene_data): ``num_samples`` pixels of each mask,
+    rotated by the pair's records, as the blind lists; a pair with an empty mask is empty.  Arguments as
+    build_within_scene_samples; -> SampleBatch."""
+    n, h, w = int(mask_a.shape[0]), int(mask_a.shape[1]), int(mask_a.shape[2])
+    dev = mask_a.device
+    lib = _lib.get()
+    ma, mb = _mask(mask_a, n, h, w, "mask_a"), _mask(mask_b, n, h, w, "mask_b")
+    ns = int(num_samples)
+    if ns < 1:
+        raise ValueError("num_samples must be >= 1")
+    params = _params(aug_params, n, dev, generator, domain_randomize, flip)
+    sd, rand, roff = _random(n, dev, generator, draws, seeds)
+    _lib.require_device(ma, mb, params, sd, rand, roff)
+    cap = n * ns
+    idx_a, idx_b, offsets, empty, typ, status = _outputs(n, cap, dev)
+    ws = torch.empty(int(lib.dcn_sample_workspace(n, h, w, 0, 0)), dtype=torch.uint8, device=dev)
+    P = _lib.ptr
+    rc = lib.dcn_across_scene_samples(n, h, w, P(ma), P(mb), ns, P(params), P(sd), P(rand), P(roff), int(data_type), P(idx_a),
+                                      P(idx_b), cap, P(offsets), P(empty), P(typ), P(status), P(ws), _lib.stream_ptr())
+    _lib.check(rc, "dcn_across_scene_samples")
+    ia, ib, mka, mkb = _images(rgb_a, rgb_b, ma, mb, params, mean, std)
+    return SampleBatch(ia, ib, idx_a, idx_b, offsets, empty, typ, status, sd, params, mka, mkb)
+
+
+def complete_samples(uv_a, uv_b, offsets, mask_a, mask_b, *, num_masked_non_matches_per_match,
+                     num_background_non_matches_per_match, use_image_b_mask_inv, generator=None, draws=None, seeds=None,
+                     aug_params=None, data_type=SYNTHETIC_MULTI_OBJECT):
+    """Non-matches and blind non-matches for match lists found elsewhere, e.g. merge.merge_synthetic_samples' uv_1 / uv_2
+    and merged masks: uv_a (int64) / uv_b (int64 or float32) ``(u, v)`` lists, pair p at ``offsets[p]:offsets[p+1]``
+    ([B + 1] tensor or sequence; a -1 capacity tail after offsets[B] is ignored); mask_a, mask_b: 0/1 [B, H, W] of the
+    frames the lists index.  ``aug_params`` (optional): rotation records to apply to lists and masks first.  A pair without
+    matches is empty.  -> SampleBatch (no images)."""
+    n, h, w = int(mask_a.shape[0]), int(mask_a.shape[1]), int(mask_a.shape[2])
+    dev = mask_a.device
+    lib = _lib.get()
+    ma, mb = _mask(mask_a, n, h, w, "mask_a"), _mask(mask_b, n, h, w, "mask_b")
+    ua, va = uv_a[0].contiguous(), uv_a[1].contiguous()
+    ub, vb = uv_b[0].contiguous(), uv_b[1].contiguous()
+    if ua.dtype != torch.int64 or va.dtype != torch.int64 or ub.dtype != vb.dtype or len({int(x.numel()) for x in
+                                                                                          (ua, va, ub, vb)}) != 1:
+        raise ValueError("uv_a must be int64, uv_b int64 or float32, all four lists of one length")
+    uv_b_dtype = _aug._uv_dtype(ub)
+    if not torch.is_tensor(offsets):
+        offsets = torch.tensor([int(o) for o in offsets], dtype=torch.int64)
+    if offsets.numel() != n + 1:
+        raise ValueError("offsets must have B + 1 = %d entries, got %d" % (n + 1, offsets.numel()))
+    off = offsets.to(device=dev, dtype=torch.int64, non_blocking=True).contiguous().view(-1)
+    k1, k2 = int(num_masked_non_matches_per_match), int(num_background_non_matches_per_match)
+    if k1 < 1 or k2 < 1:
+        raise ValueError("the non-matches per match must be >= 1")
+    params = None if aug_params is None else _params(aug_params, n, dev, None, False, True)
+    sd, rand, roff = _random(n, dev, generator, draws, seeds)
+    _lib.require_device(ua, va, ub, vb, off, ma, mb, params, sd, rand, roff)
+    count = int(ua.numel())
+    cap = count * (1 + k1 + k2) + n * h * w
+    idx_a, idx_b, offsets_out, empty, typ, status = _outputs(n, cap, dev)
+    ws = torch.empty(int(lib.dcn_sample_workspace(n, h, w, 0, count)), dtype=torch.uint8, device=dev)
+    P = _lib.ptr
+    rc = lib.dcn_complete_samples(n, h, w, P(ua), P(va), P(ub), P(vb), uv_b_dtype, P(off), count, P(ma), P(mb), k1, k2,
+                                  MASK_INV if use_image_b_mask_inv else 0, P(params), P(sd), P(rand), P(roff), int(data_type),
+                                  P(idx_a), P(idx_b), cap, P(offsets_out), P(empty), P(typ), P(status), P(ws),
+                                  _lib.stream_ptr())
+    _lib.check(rc, "dcn_complete_samples")
+    return SampleBatch(None, None, idx_a, idx_b, offsets_out, empty, typ, status, sd, params, None, None)

@@ -97,3 +97,21 @@ def create_non_correspondences(uv_b_matches, img_b_shape, num_non_matches_per_ma
     if u is None:                                                           # no mask, or an empty one (:313-316, :325)
         u, v = _pg.sample_pixels(torch.rand(2, n, device=dev), n, w, h)
     return u.view(num_matches, num_non_matches_per_match), v.view(num_matches, num_non_matches_per_match)
+
+
+def random_sample_from_masked_image_torch(img_mask, num_samples):
+    """:92-121 for a DEVICE mask [H, W]: ``(u, v)`` int64 device tensors of ``num_samples`` pixels drawn from the non-zero
+    pixels (``torch.rand(num_samples)``, index ``floor(r * count)``), or ``(None, None)`` for an empty mask (one host read of
+    the count).  Host masks (numpy or CPU tensors) go to the reference's own function."""
+    if not (torch.is_tensor(img_mask) and img_mask.is_cuda):
+        ref = _ref.get()
+        if ref is None:
+            raise ValueError("this module only samples device masks; host masks go to the reference's function (%s)"
+                             % _ref.why_not())
+        return ref.random_sample_from_masked_image_torch(img_mask, num_samples)
+    h, w = int(img_mask.shape[0]), int(img_mask.shape[1])
+    lst, cnt = _pg.mask_nonzero(img_mask)
+    if int(cnt.item()) == 0:
+        return (None, None)
+    u, v = _pg.sample_pixels(torch.rand(num_samples, device=img_mask.device), num_samples, w, h, lst, cnt)
+    return u.long(), v.long()
