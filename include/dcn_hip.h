@@ -721,6 +721,80 @@ int dcn_across_scene_samples(int n, int h, int w, const uint8_t* mask_a, const u
                              int data_type, int64_t* idx_a, int64_t* idx_b, int64_t capacity, int64_t* offsets, uint8_t* empty,
                              int32_t* type, int32_t* status, void* workspace, void* stream);
 
+/* =====================================================================================================
+ * 10. Frame store -- replaces, for frames kept in device memory, the frame choice of the reference's loader
+ *     (dense_correspondence/dataset/spartan_dataset_masked.py: the five type wrappers :543-575, :860-905 and the helpers
+ *     get_random_image_index :408-420, get_random_single_object_scene_name :442-451, get_different_scene_for_object
+ *     :453-474, get_two_different_object_ids :476-494, get_random_multi_object_scene_name :496-502;
+ *     dense_correspondence_dataset_masked.py get_img_idx_with_different_pose :260-287) and the decode / stack / upload of
+ *     the chosen frames.
+ *     Store tables (struct dcn_frame_store, all DEVICE pointers, passed to the entry points as a HOST pointer to the struct):
+ *       rgb uint8 [F][h][w][3]; depth uint16 [F][h][w] millimetres; mask uint8 [F][h][w] (0 / 1)
+ *       scene_first_frame int32 [S + 1]: scene s owns frames [scene_first_frame[s], scene_first_frame[s+1]) (>= 1 each),
+ *                  in the order of the reference's pose_data keys (a position drawn by random.choice IS the frame's offset)
+ *       scene_object int32 [S]: the scene's object, or -1 for a multi-object scene
+ *       object_scene_offsets int32 [O + 1], object_scenes int32 [...]: object o's scene list, in the reference's order
+ *       multi_scenes int32 [M]: the multi-object scenes, in the reference's order
+ *       scene_cams float [S][18]: K (3x3) then K^-1, row-major, fp32 of the float64 K and of its float64 inverse
+ *       poses double [F][16]: camera-to-world, row-major
+ *     No entry point needs a workspace.
+ * ===================================================================================================== */
+struct dcn_frame_store {
+    int64_t num_frames;
+    int32_t num_scenes, num_objects, num_multi, h, w;
+    const uint8_t* rgb;
+    const uint16_t* depth;
+    const uint8_t* mask;
+    const int32_t* scene_first_frame;
+    const int32_t* scene_object;
+    const int32_t* object_scene_offsets;
+    const int32_t* object_scenes;
+    const int32_t* multi_scenes;
+    const float* scene_cams;
+    const double* poses;
+};
+#define DCN_FRAME_CAM_FLOATS 18
+#define DCN_FRAME_SLOTS 4           /* frames [n][4]: a, b (a1, a2, b1, b2 for SYNTHETIC_MULTI_OBJECT; -1 past 2 otherwise) */
+/* Replay words, per pair: draws int32 [n][DCN_FRAME_DRAW_HEADER + 2 * num_attempts], each the POSITION that the reference's
+ * random.choice / np.random.choice returned in its list (get_random_image_index: the second of its two random.choice calls) */
+#define DCN_FRAME_DRAW_OBJECT_A 0   /* random.choice over the objects; np.random.choice(..., 2)[0] (DIFFERENT_OBJECT, SYNTHETIC) */
+#define DCN_FRAME_DRAW_OBJECT_B 1   /* np.random.choice(..., 2)[1] over the objects (DIFFERENT_OBJECT, SYNTHETIC) */
+#define DCN_FRAME_DRAW_SCENE_A 2    /* random.choice over object a's scenes (MULTI_OBJECT: over the multi-object scenes) */
+#define DCN_FRAME_DRAW_SCENE_B 3    /* random.choice over object b's scenes; SINGLE_OBJECT_ACROSS_SCENE: np.random.choice[0] */
+#define DCN_FRAME_DRAW_SCENE_B2 4   /* SINGLE_OBJECT_ACROSS_SCENE: np.random.choice(..., 2)[1] over the object's scenes */
+#define DCN_FRAME_DRAW_FRAME_A 5    /* image a (a1) in scene a */
+#define DCN_FRAME_DRAW_FRAME_B 6    /* image b in scene b (across types); image b1 (SYNTHETIC) */
+#define DCN_FRAME_DRAW_HEADER 8     /* then num_attempts words: image b (a2) candidates in scene a; then num_attempts: b2's */
+#define DCN_FRAME_BAD_INDEX 1       /* status: a table entry or a frame index out of range (that frame reads as zeros) */
+#define DCN_FRAME_BAD_DRAWS 2       /* status: a replay position outside its list, or np.random.choice's two positions equal */
+#define DCN_FRAME_NO_CANDIDATES 4   /* status: the type has no eligible object or scene (no multi-object scene, an object with
+                                     * one scene for SINGLE_OBJECT_ACROSS_SCENE, fewer than two objects); the pair is empty */
+/* One launch for n pairs of one data_type (SpartanDatasetDataType numbering, as section 9: 0 SINGLE_OBJECT_WITHIN_SCENE,
+ * 1 SINGLE_OBJECT_ACROSS_SCENE, 2 DIFFERENT_OBJECT, 3 MULTI_OBJECT, 4 SYNTHETIC_MULTI_OBJECT), one wavefront per pair.
+ * Image b of a within-scene choice is get_img_idx_with_different_pose(scene, pose a, threshold, angle_threshold,
+ * num_attempts): the first of num_attempts uniform frames of the scene whose translation is more than `threshold` from pose
+ * a's (float64, sqrt of the sum of squares) or whose angle 2 acos(clamp((tr(R_a^T R_b) - 1) / 2, -1, 1)) -- the reference's
+ * 2 arccos(2 <q_a, q_b>^2 - 1), in radians -- exceeds angle_threshold (never, when angle_threshold >= 2 pi).  No such frame:
+ * the pair is empty and its missing frame b is frame a (a2 := a1, b2 := b1 for SYNTHETIC).  Random numbers: seeds != NULL: seeds
+ * [n] int64, word k of pair p is a counter-based hash of (seed, k) mapped onto the list's length (np.random.choice's two
+ * distinct positions: the second over the other n - 1); seeds == NULL: draws (replay, layout above).
+ * Outputs: frames int32 [n][DCN_FRAME_SLOTS] global frame indices; empty uint8 [n]; scenes int32 [n][2] (scene of a / a1,
+ * of b / b1); objects int32 [n][2] (-1: multi-object); status int32 [1], DCN_FRAME_* bits (written, not accumulated).
+ * 1 <= n <= 65536, 1 <= num_attempts <= 4096. */
+int dcn_select_frames(int n, int data_type, const struct dcn_frame_store* store, int num_attempts, double threshold,
+                      double angle_threshold, const int64_t* seeds, const int32_t* draws, int32_t* frames, uint8_t* empty,
+                      int32_t* scenes, int32_t* objects, int32_t* status, void* stream);
+/* One launch: copies slot k (0 <= k < frames_per_pair, 2 or 4) of every pair, frame frames[p][k], to rgb [k][n][h][w][3],
+ * depth [k][n][h][w], mask [k][n][h][w] (any of the three may be NULL), 16-byte loads and stores where the planes allow.
+ * An empty pair (empty may be NULL) gets zero depth in all its slots, so no match survives the reprojection test of section 9.
+ * cams (may be NULL): float [frames_per_pair / 2][n][DCN_SAMPLE_CAM_FLOATS], row j of pair p for slots (2j, 2j+1): the
+ * scene_cams row of slot 2j's scene, pose of slot 2j as fp32, and the rigid inverse of slot 2j+1's pose computed in float64
+ * (R^T; -(R^T t) summed left to right, no contraction) then rounded to fp32 -- the rows of section 9's cams.  A frame index
+ * outside [0, num_frames) ORs DCN_FRAME_BAD_INDEX into *status (accumulated: the selection's word) and reads as zeros. */
+int dcn_gather_frames(int n, int frames_per_pair, const struct dcn_frame_store* store, const int32_t* frames,
+                      const uint8_t* empty, uint8_t* rgb, uint16_t* depth, uint8_t* mask, float* cams, int32_t* status,
+                      void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -30,6 +30,13 @@ class ConvDesc(ctypes.Structure):
                                               "pad", "dil", "ldc", "group_rows")]
 
 
+class FrameStoreDesc(ctypes.Structure):
+    """struct dcn_frame_store"""
+    _fields_ = [("num_frames", c_int64)] + [(k, ctypes.c_int32) for k in ("num_scenes", "num_objects", "num_multi", "h", "w")] \
+        + [(k, c_void_p) for k in ("rgb", "depth", "mask", "scene_first_frame", "scene_object", "object_scene_offsets",
+                                   "object_scenes", "multi_scenes", "scene_cams", "poses")]
+
+
 SYMBOLS = {
     # name: (restype, argtypes)
     "dcn_version": (c_char_p, []),
@@ -191,6 +198,9 @@ SYMBOLS = {
                                  + [c_int, c_void_p, c_void_p, c_int64] + [c_void_p] * 6),
     "dcn_merge_prune": (c_int, [c_int, c_int, c_int] + [c_void_p] * 10 + [c_int64] + [c_void_p] * 5 + [c_int64, c_int]
                         + [c_void_p] * 9),
+    "dcn_select_frames": (c_int, [c_int, c_int, ctypes.POINTER(FrameStoreDesc), c_int, ctypes.c_double, ctypes.c_double]
+                          + [c_void_p] * 8),
+    "dcn_gather_frames": (c_int, [c_int, c_int, ctypes.POINTER(FrameStoreDesc)] + [c_void_p] * 8),
 }
 
 ERRORS = {-1: "DCN_E_INVALID (bad argument)", -2: "DCN_E_LAUNCH (kernel launch failed)",

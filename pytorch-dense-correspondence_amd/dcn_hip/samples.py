@@ -185,7 +185,7 @@ def build_within_scene_samples(depth_a, depth_b, mask_a, mask_b, pose_a, pose_b,
                                num_matching_attempts, sample_matches_only_off_mask, num_masked_non_matches_per_match,
                                num_background_non_matches_per_match, use_image_b_mask_inv, domain_randomize=False, flip=True,
                                mean=_aug.DEFAULT_IMAGE_MEAN, std=_aug.DEFAULT_IMAGE_STD_DEV, generator=None, draws=None,
-                               aug_params=None, seeds=None, data_type=SINGLE_OBJECT_WITHIN_SCENE):
+                               aug_params=None, seeds=None, data_type=SINGLE_OBJECT_WITHIN_SCENE, cameras=None):
     """B within-scene samples on the device (get_within_scene_data).
 
     depth_a, depth_b: 16-bit [B, H, W] millimetres (int16 / uint16, same bits); mask_a, mask_b: 0/1 [B, H, W]; pose_a, pose_b:
@@ -193,7 +193,8 @@ def build_within_scene_samples(depth_a, depth_b, mask_a, mask_b, pose_a, pose_b,
     rgb_a, rgb_b: optional uint8 [B, H, W, 3] -> normalized network inputs of the augmented images.  ``aug_params``: [2B, 16]
     augmentation records (augment.draw_params layout) to replay, otherwise drawn with ``generator`` (``domain_randomize``,
     ``flip``).  ``draws``: the reference's torch.rand streams per site and pair (replay; see pack_draws), otherwise per-pair
-    ``seeds`` (drawn with ``generator`` when None).
+    ``seeds`` (drawn with ``generator`` when None).  ``cameras``: the camera rows [B, 50] fp32 on the device (K, K^-1, pose a,
+    pose b^-1, e.g. frames.FrameBatch.cams[0]) in place of K / pose_a / pose_b, which are then not read.
 
     -> SampleBatch.  Launches: the sample chain (about ten small kernels) and, with RGB, one augmentation launch; no host
     synchronization."""
@@ -207,7 +208,13 @@ def build_within_scene_samples(depth_a, depth_b, mask_a, mask_b, pose_a, pose_b,
         raise ValueError("num_matching_attempts and the non-matches per match must be >= 1")
     params = _params(aug_params, n, dev, generator, domain_randomize, flip)
     sd, rand, roff = _random(n, dev, generator, draws, seeds)
-    cams = _cameras(K, pose_a, pose_b, n, dev)
+    if cameras is None:
+        cams = _cameras(K, pose_a, pose_b, n, dev)
+    else:
+        cams = cameras
+        if tuple(cams.shape) != (n, CAM_FLOATS) or cams.dtype != torch.float32 or not cams.is_contiguous():
+            raise ValueError("cameras must be contiguous float32 [%d, %d], got %s %s" % (n, CAM_FLOATS, cams.dtype,
+                                                                                      tuple(cams.shape)))
     _lib.require_device(da, db, ma, mb, cams, params, sd, rand, roff)
     cap = n * (A * (1 + k1 + k2) + h * w)
     idx_a, idx_b, offsets, empty, typ, status = _outputs(n, cap, dev)
