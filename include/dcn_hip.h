@@ -170,6 +170,52 @@ int dcn_contrastive_loss_backward_saved_exact(int num_pairs, int64_t hw, int d, 
 /* Stream-ordered fill of n bytes (n % 4 == 0) with a byte value, as a kernel (an ordinary node under hipGraph capture). */
 int dcn_fill_bytes(void* p, int byte_value, size_t n, void* stream);
 
+/* -----------------------------------------------------------------------------------------------------
+ * 1b. The same loss for a batch built on the device (section 9, dcn_concat_samples): nothing is known on the host but BOUNDS.
+ *   offsets_dev [4 * num_pairs + 1] int64 and types_dev [num_pairs] int32 are read on the device only.  types_dev[p] is pair
+ *   p's data type in SpartanDatasetDataType numbering (0 SINGLE_OBJECT_WITHIN_SCENE, 1 SINGLE_OBJECT_ACROSS_SCENE,
+ *   2 DIFFERENT_OBJECT, 3 MULTI_OBJECT, 4 SYNTHETIC_MULTI_OBJECT) and selects cfgs[types_dev[p]] -- margins, hinge modes,
+ *   pixel weights, hard-negative scaling and composition -- for that pair; -1 leaves the pair out (the reference's
+ *   return_empty_data sample, which its training loop skips, training.py:304-306).
+ *   Host bounds: no list is longer than max_list_len, no pair has more than max_pair_len entries in its four lists, and
+ *   idx_a / idx_b hold `capacity` entries (entries past offsets[4 * num_pairs] are never read).  The launches are shaped by
+ *   max_list_len, the records by capacity: pair_records holds dcn_loss_saved_floats(capacity, d) floats (NULL: none kept).
+ *   workspace: dcn_loss_workspace_bytes(num_pairs, max_list_len) bytes.  num_pairs <= 16383.
+ *     loss      [1]  = (sum of loss_p over the pairs kept) / max(num_valid, 1); the backward scales by the same 1 / num_valid
+ *     num_valid [1] int32: the pairs kept
+ *     terms / sums / hard_neg as section 1; a pair left out has zero rows there and in both gradient maps, whatever its
+ *       offsets say
+ *     status    [1] int32: DCN_LOSS_BAD_* bits, written (not accumulated) by the last kernel of the forward call
+ *   A batch of one type without a pair left out gives the bits of dcn_contrastive_loss_forward_save / _backward_saved_exact
+ *   with that type's configuration (same partial layout, same summation orders).
+ *   dcn_contrastive_loss_mixed_backward_saved_exact: DCN_E_UNSUPPORTED when max_pair_len >= 2^22 (use the float path). */
+#define DCN_LOSS_NUM_TYPES 5
+#define DCN_LOSS_BAD_INDEX 1        /* status: an index outside [0, HW) (that pixel pair is skipped), as section 1 */
+#define DCN_LOSS_BAD_TYPE 2         /* status: a type outside {-1, 0 .. 4} (the pair is left out) */
+#define DCN_LOSS_BAD_BOUNDS 4       /* status: a list longer than max_list_len, a pair with more than max_pair_len entries,
+                                       offsets that decrease, or offsets[4 * num_pairs] > capacity (the pairs concerned are
+                                       left out; nothing is read outside idx_a / idx_b [0, capacity)) */
+#define DCN_LOSS_BAD_PIXEL_LAYOUT 8 /* status: pixel-distance weighting for a pair whose non-match count is not a whole
+                                       multiple of its match count (pixelwise_contrastive_loss.py:321-325) */
+int dcn_contrastive_loss_mixed_forward(const float* desc_a, const float* desc_b, int num_pairs, int64_t hw, int d,
+                                       const int64_t* idx_a, const int64_t* idx_b, const int64_t* offsets_dev,
+                                       const int32_t* types_dev, const dcn_loss_config* cfgs, int64_t max_list_len,
+                                       int64_t max_pair_len, int64_t capacity, float* terms, float* sums, int32_t* hard_neg,
+                                       float* loss, int32_t* num_valid, int32_t* status, void* workspace, float* pair_records,
+                                       void* stream);
+int dcn_contrastive_loss_mixed_backward_saved(int num_pairs, int64_t hw, int d, const int64_t* idx_a, const int64_t* idx_b,
+                                              const int64_t* offsets_dev, const int32_t* types_dev, const dcn_loss_config* cfgs,
+                                              int64_t max_list_len, int64_t max_pair_len, int64_t capacity,
+                                              const int32_t* hard_neg, const int32_t* num_valid, const float* grad_loss,
+                                              const float* pair_records, int prefilled, float* grad_a, float* grad_b,
+                                              void* stream);
+int dcn_contrastive_loss_mixed_backward_saved_exact(int num_pairs, int64_t hw, int d, const int64_t* idx_a, const int64_t* idx_b,
+                                                    const int64_t* offsets_dev, const int32_t* types_dev,
+                                                    const dcn_loss_config* cfgs, int64_t max_list_len, int64_t max_pair_len,
+                                                    int64_t capacity, const int32_t* hard_neg, const int32_t* num_valid,
+                                                    const float* grad_loss, const float* pair_records, void* workspace,
+                                                    float* grad_a, float* grad_b, void* stream);
+
 /* Triplet variant (pixelwise_contrastive_loss.py:104-129, loss_composer.py:145-166):
  *   loss = 1/n * sum_i sum_k max(0, (a_k - m_k)^2 - (a_k - q_k)^2 + alpha),   a = A[non_a[i]], m = B[match_b[i / (n / n_match)]],
  *   q = B[non_b[i]]  -- hinge per descriptor component, exactly as the reference computes it.  n % n_match == 0.
@@ -720,6 +766,20 @@ int dcn_across_scene_samples(int n, int h, int w, const uint8_t* mask_a, const u
                              const int32_t* aug_params, const int64_t* seeds, const float* rand, const int64_t* rand_offsets,
                              int data_type, int64_t* idx_a, int64_t* idx_b, int64_t capacity, int64_t* offsets, uint8_t* empty,
                              int32_t* type, int32_t* status, void* workspace, void* stream);
+
+/* Joins the outputs of `groups` (<= DCN_CONCAT_MAX_GROUPS) calls above -- e.g. one per data type -- into one batch of
+ * sum n[g] <= 1024 pairs, in the order given: host arrays [groups] of the group sizes n, of the DEVICE pointers idx_a, idx_b,
+ * offsets ([4 n[g] + 1]), status_in (the array or single entries may be NULL) and of the groups' capacities.  Outputs as
+ * above: idx_a_out / idx_b_out int64 [capacity], 16-byte aligned, pair p's list t at [offsets_out[4p+t], offsets_out[4p+t+1]),
+ * -1 from offsets_out[4 * sum n] on (capacity >= the sum of the groups' capacities always holds them); offsets_out
+ * [4 * sum n + 1]; status [1] = the groups' words OR-ed, | DCN_SAMPLE_BAD_OFFSETS for a group whose offsets do not increase
+ * from 0 within its capacity (its pairs keep their slots with empty lists) or when the joined lists exceed `capacity`.  Two
+ * launches, no host synchronisation.  type / empty and the images are per-pair arrays: the caller concatenates them. */
+#define DCN_CONCAT_MAX_GROUPS 8
+int dcn_concat_samples(int groups, const int* n, const int64_t* const* idx_a, const int64_t* const* idx_b,
+                       const int64_t* const* offsets, const int64_t* capacity_in, const int32_t* const* status_in,
+                       int64_t* idx_a_out, int64_t* idx_b_out, int64_t capacity, int64_t* offsets_out, int32_t* status,
+                       void* stream);
 
 /* =====================================================================================================
  * 10. Frame store -- replaces, for frames kept in device memory, the frame choice of the reference's loader

@@ -43,14 +43,16 @@ __device__ __forceinline__ float pixel_weight(int64_t gt, int64_t nb, int width,
     return fminf(sqrtf(du * du + dv * dv), m_pixel) / m_pixel;
 }
 
-// grid = (chunks, 4*num_pairs).  Every workgroup writes its partial, chunks beyond the list's end write zeros.
+// The forward pass of ONE workgroup: chunk blockIdx.x of segment blockIdx.y = 4 * pair + list, whose entries are
+// [beg, beg + len) of idx_a / idx_b (len == 0: the workgroup writes zero partials -- a chunk beyond the list's end, or, in
+// the mixed-type call below, a pair that is left out).  Shared by loss_fwd_kernel and loss_fwd_mixed_kernel.
 template <int LP, bool SINGLE>
-__global__ void __launch_bounds__(kThreads)
-loss_fwd_kernel(const float* __restrict__ A, const float* __restrict__ B, int64_t hw, int D,
-                const int64_t* __restrict__ idx_a, const int64_t* __restrict__ idx_b,
-                const int64_t* __restrict__ offsets, dcn_loss_config cfg, double* __restrict__ part_sum,
-                int* __restrict__ part_cnt, float* __restrict__ per_term, int* __restrict__ part_oob,
-                float* __restrict__ rec_d, float* __restrict__ rec_s) {
+__device__ __forceinline__ void
+loss_fwd_body(const float* __restrict__ A, const float* __restrict__ B, int64_t hw, int D,
+              const int64_t* __restrict__ idx_a, const int64_t* __restrict__ idx_b,
+              const int64_t* __restrict__ offsets, const dcn_loss_config& cfg, int64_t beg, int64_t len,
+              double* __restrict__ part_sum, int* __restrict__ part_cnt, float* __restrict__ per_term,
+              int* __restrict__ part_oob, float* __restrict__ rec_d, float* __restrict__ rec_s) {
     // rec_d [total][D], rec_s [total] (optional, together): per pixel pair the difference vector a - b and the factor s with
     //     d loss / d a = coef(list, image pair) * s * (a - b)      (= - d loss / d b)
     // -- everything of the pair's gradient that does not depend on the hard-negative counts of the whole image pair.  The
@@ -64,7 +66,6 @@ loss_fwd_kernel(const float* __restrict__ A, const float* __restrict__ B, int64_
     __syncthreads();
     constexpr int GROUPS = kThreads / LP, PPB = GROUPS * kItems;
     const int seg = blockIdx.y, p = seg >> 2, t = seg & 3;
-    const int64_t beg = offsets[seg], len = offsets[seg + 1] - beg;
     const int64_t chunk0 = (int64_t)blockIdx.x * PPB;
     const int grp = threadIdx.x / LP, sub = threadIdx.x % LP;
     double sum = 0.0;
@@ -145,6 +146,19 @@ loss_fwd_kernel(const float* __restrict__ A, const float* __restrict__ B, int64_
         part_cnt[(int64_t)seg * gridDim.x + blockIdx.x] = bc;
         part_oob[(int64_t)seg * gridDim.x + blockIdx.x] = s_oob;
     }
+}
+
+// grid = (chunks, 4*num_pairs).  Every workgroup writes its partial, chunks beyond the list's end write zeros.
+template <int LP, bool SINGLE>
+__global__ void __launch_bounds__(kThreads)
+loss_fwd_kernel(const float* __restrict__ A, const float* __restrict__ B, int64_t hw, int D,
+                const int64_t* __restrict__ idx_a, const int64_t* __restrict__ idx_b,
+                const int64_t* __restrict__ offsets, dcn_loss_config cfg, double* __restrict__ part_sum,
+                int* __restrict__ part_cnt, float* __restrict__ per_term, int* __restrict__ part_oob,
+                float* __restrict__ rec_d, float* __restrict__ rec_s) {
+    const int64_t beg = offsets[blockIdx.y], len = offsets[blockIdx.y + 1] - beg;
+    loss_fwd_body<LP, SINGLE>(A, B, hw, D, idx_a, idx_b, offsets, cfg, beg, len, part_sum, part_cnt, per_term, part_oob, rec_d,
+                              rec_s);
 }
 
 // Scale factors shared by the finalize and the backward kernel (loss_composer.py:107-134, :179-187, :205-211).
@@ -274,14 +288,10 @@ loss_mean_kernel(const double* __restrict__ pair_loss, const int* __restrict__ p
 // few pairs (the training configurations: 1-8 per step): ONE workgroup -- each wavefront reduces (pair, term) sums with a
 // fixed shuffle tree, then one work-item per pair composes its 5-tuple and work-item 0 averages in pair order and writes the
 // status word: one launch instead of three (status clear, finalize, mean), no serial walk over the pairs
-__global__ void __launch_bounds__(kThreads)
-loss_finalize_all_kernel(const double* __restrict__ part_sum, const int* __restrict__ part_cnt, const int* __restrict__ part_oob,
-                         int chunks, int num_pairs, const int64_t* __restrict__ offsets, dcn_loss_config cfg,
-                         float* __restrict__ terms, float* __restrict__ sums, int* __restrict__ hard_neg,
-                         double* __restrict__ pair_loss, float* __restrict__ loss, int* __restrict__ status) {
-    __shared__ double s_S[8][4];
-    __shared__ int s_h[8][4];
-    __shared__ int s_o[8][4];
+// (the reduction of loss_finalize_all_kernel, shared with its mixed-type twin: the same order, so the same bits)
+__device__ __forceinline__ void reduce_all_partials(const double* __restrict__ part_sum, const int* __restrict__ part_cnt,
+                                                    const int* __restrict__ part_oob, int chunks, int num_pairs,
+                                                    double (*s_S)[4], int (*s_h)[4], int (*s_o)[4]) {
     const int lane = threadIdx.x & (dcn::kWave - 1), wv = threadIdx.x / dcn::kWave;
     for (int q = wv; q < 4 * num_pairs; q += kThreads / dcn::kWave) {
         double a = 0.0;
@@ -297,6 +307,17 @@ loss_finalize_all_kernel(const double* __restrict__ part_sum, const int* __restr
         if (lane == 0) { s_S[q >> 2][q & 3] = a; s_h[q >> 2][q & 3] = c; s_o[q >> 2][q & 3] = o; }
     }
     __syncthreads();
+}
+
+__global__ void __launch_bounds__(kThreads)
+loss_finalize_all_kernel(const double* __restrict__ part_sum, const int* __restrict__ part_cnt, const int* __restrict__ part_oob,
+                         int chunks, int num_pairs, const int64_t* __restrict__ offsets, dcn_loss_config cfg,
+                         float* __restrict__ terms, float* __restrict__ sums, int* __restrict__ hard_neg,
+                         double* __restrict__ pair_loss, float* __restrict__ loss, int* __restrict__ status) {
+    __shared__ double s_S[8][4];
+    __shared__ int s_h[8][4];
+    __shared__ int s_o[8][4];
+    reduce_all_partials(part_sum, part_cnt, part_oob, chunks, num_pairs, s_S, s_h, s_o);
     if ((int)threadIdx.x < num_pairs) compose_pair(threadIdx.x, s_S[threadIdx.x], s_h[threadIdx.x], offsets, cfg, terms, sums, hard_neg, pair_loss);
     __syncthreads();
     if (threadIdx.x == 0) {
@@ -401,15 +422,16 @@ loss_bwd_kernel(const float* __restrict__ A, const float* __restrict__ B, int64_
 // Backward from the records the forward pass saved (loss_fwd_kernel: rec_d, rec_s): per pixel pair two int64 indices, the
 // factor and the D-float difference -- coalesced streams -- then the same run of D fp32 atomics per descriptor as above.  No
 // descriptor is gathered again.  grid = (chunks, 4*num_pairs).
+// (the three *_body functions below: one workgroup's share of segment blockIdx.y = 4 * pair + list, entries [beg, beg + len),
+//  the upstream gradient divided by `denom` pairs; shared by the kernels of the one-type call and of the mixed-type call)
 template <int LP, bool SINGLE>
-__global__ void __launch_bounds__(kThreads)
-loss_bwd_saved_kernel(int64_t hw, int D, int num_pairs, const int64_t* __restrict__ idx_a, const int64_t* __restrict__ idx_b,
-                      const int64_t* __restrict__ offsets, dcn_loss_config cfg, const int* __restrict__ hard_neg,
-                      const float* __restrict__ grad_loss, const float* __restrict__ rec_d, const float* __restrict__ rec_s,
-                      float* __restrict__ gA, float* __restrict__ gB) {
+__device__ __forceinline__ void
+loss_bwd_saved_body(int64_t hw, int D, float denom, const int64_t* __restrict__ idx_a, const int64_t* __restrict__ idx_b,
+                    const int64_t* __restrict__ offsets, const dcn_loss_config& cfg, int64_t beg, int64_t len,
+                    const int* __restrict__ hard_neg, const float* __restrict__ grad_loss, const float* __restrict__ rec_d,
+                    const float* __restrict__ rec_s, float* __restrict__ gA, float* __restrict__ gB) {
     constexpr int GROUPS = kThreads / LP, PPB = GROUPS * kItems;
     const int seg = blockIdx.y, p = seg >> 2, t = seg & 3;
-    const int64_t beg = offsets[seg], len = offsets[seg + 1] - beg;
     const int64_t chunk0 = (int64_t)blockIdx.x * PPB;
     if (chunk0 >= len) return;
     const int grp = threadIdx.x / LP, sub = threadIdx.x % LP;
@@ -420,7 +442,7 @@ loss_bwd_saved_kernel(int64_t hw, int D, int num_pairs, const int64_t* __restric
     const PairScales sc = pair_scales(cfg, h, lens);
     float coef = t == DCN_LIST_MATCH ? sc.match_coef : (t == DCN_LIST_BLIND ? sc.blind_coef : sc.nonmatch_coef);
     if (coef == 0.f) return;
-    coef *= grad_loss[0] / (float)num_pairs;
+    coef *= grad_loss[0] / denom;
     float* gAp = gA + (int64_t)p * hw * D;
     float* gBp = gB + (int64_t)p * hw * D;
 #pragma unroll
@@ -447,6 +469,17 @@ loss_bwd_saved_kernel(int64_t hw, int D, int num_pairs, const int64_t* __restric
     }
 }
 
+template <int LP, bool SINGLE>
+__global__ void __launch_bounds__(kThreads)
+loss_bwd_saved_kernel(int64_t hw, int D, int num_pairs, const int64_t* __restrict__ idx_a, const int64_t* __restrict__ idx_b,
+                      const int64_t* __restrict__ offsets, dcn_loss_config cfg, const int* __restrict__ hard_neg,
+                      const float* __restrict__ grad_loss, const float* __restrict__ rec_d, const float* __restrict__ rec_s,
+                      float* __restrict__ gA, float* __restrict__ gB) {
+    const int64_t beg = offsets[blockIdx.y], len = offsets[blockIdx.y + 1] - beg;
+    loss_bwd_saved_body<LP, SINGLE>(hw, D, (float)num_pairs, idx_a, idx_b, offsets, cfg, beg, len, hard_neg, grad_loss, rec_d,
+                                    rec_s, gA, gB);
+}
+
 // ---- the same backward pass, ORDER-INDEPENDENT (round 6): every contribution v is converted to 64-bit fixed point under a
 // per-image-pair power-of-two scale and accumulated with INTEGER atomics -- integer addition is associative, so the dense
 // gradient maps carry the same bits whatever order the hardware retires the atomics in (the fp32 atomics above make the loss
@@ -467,13 +500,12 @@ __device__ __forceinline__ double exact_scale(float vmax) {      // 2^e with vma
 }
 
 template <int LP, bool SINGLE>
-__global__ void __launch_bounds__(kThreads)
-loss_bwd_vmax_kernel(int D, int num_pairs, const int64_t* __restrict__ offsets, dcn_loss_config cfg,
-                     const int* __restrict__ hard_neg, const float* __restrict__ grad_loss, const float* __restrict__ rec_d,
-                     const float* __restrict__ rec_s, unsigned* __restrict__ vmax_bits) {
+__device__ __forceinline__ void
+loss_bwd_vmax_body(int D, float denom, const int64_t* __restrict__ offsets, const dcn_loss_config& cfg, int64_t beg, int64_t len,
+                   const int* __restrict__ hard_neg, const float* __restrict__ grad_loss, const float* __restrict__ rec_d,
+                   const float* __restrict__ rec_s, unsigned* __restrict__ vmax_bits) {
     constexpr int GROUPS = kThreads / LP, PPB = GROUPS * kItems;
     const int seg = blockIdx.y, p = seg >> 2, t = seg & 3;
-    const int64_t beg = offsets[seg], len = offsets[seg + 1] - beg;
     const int64_t chunk0 = (int64_t)blockIdx.x * PPB;
     if (chunk0 >= len) return;
     const int grp = threadIdx.x / LP, sub = threadIdx.x % LP;
@@ -484,7 +516,7 @@ loss_bwd_vmax_kernel(int D, int num_pairs, const int64_t* __restrict__ offsets, 
     const PairScales sc = pair_scales(cfg, h, lens);
     float coef = t == DCN_LIST_MATCH ? sc.match_coef : (t == DCN_LIST_BLIND ? sc.blind_coef : sc.nonmatch_coef);
     if (coef == 0.f) return;
-    coef *= grad_loss[0] / (float)num_pairs;
+    coef *= grad_loss[0] / denom;
     float m = 0.f;
     bool bad = false;
 #pragma unroll
@@ -511,15 +543,23 @@ loss_bwd_vmax_kernel(int D, int num_pairs, const int64_t* __restrict__ offsets, 
 
 template <int LP, bool SINGLE>
 __global__ void __launch_bounds__(kThreads)
-loss_bwd_saved_exact_kernel(int64_t hw, int D, int num_pairs, const int64_t* __restrict__ idx_a,
-                            const int64_t* __restrict__ idx_b, const int64_t* __restrict__ offsets, dcn_loss_config cfg,
-                            const int* __restrict__ hard_neg, const float* __restrict__ grad_loss,
-                            const float* __restrict__ rec_d, const float* __restrict__ rec_s,
-                            const float* __restrict__ vmax, unsigned long long* __restrict__ accA,
-                            unsigned long long* __restrict__ accB) {
+loss_bwd_vmax_kernel(int D, int num_pairs, const int64_t* __restrict__ offsets, dcn_loss_config cfg,
+                     const int* __restrict__ hard_neg, const float* __restrict__ grad_loss, const float* __restrict__ rec_d,
+                     const float* __restrict__ rec_s, unsigned* __restrict__ vmax_bits) {
+    const int64_t beg = offsets[blockIdx.y], len = offsets[blockIdx.y + 1] - beg;
+    loss_bwd_vmax_body<LP, SINGLE>(D, (float)num_pairs, offsets, cfg, beg, len, hard_neg, grad_loss, rec_d, rec_s, vmax_bits);
+}
+
+template <int LP, bool SINGLE>
+__device__ __forceinline__ void
+loss_bwd_saved_exact_body(int64_t hw, int D, float denom, const int64_t* __restrict__ idx_a,
+                          const int64_t* __restrict__ idx_b, const int64_t* __restrict__ offsets, const dcn_loss_config& cfg,
+                          int64_t beg, int64_t len, const int* __restrict__ hard_neg, const float* __restrict__ grad_loss,
+                          const float* __restrict__ rec_d, const float* __restrict__ rec_s,
+                          const float* __restrict__ vmax, unsigned long long* __restrict__ accA,
+                          unsigned long long* __restrict__ accB) {
     constexpr int GROUPS = kThreads / LP, PPB = GROUPS * kItems;
     const int seg = blockIdx.y, p = seg >> 2, t = seg & 3;
-    const int64_t beg = offsets[seg], len = offsets[seg + 1] - beg;
     const int64_t chunk0 = (int64_t)blockIdx.x * PPB;
     if (chunk0 >= len) return;
     const double scale = exact_scale(vmax[p]);
@@ -532,7 +572,7 @@ loss_bwd_saved_exact_kernel(int64_t hw, int D, int num_pairs, const int64_t* __r
     const PairScales sc = pair_scales(cfg, h, lens);
     float coef = t == DCN_LIST_MATCH ? sc.match_coef : (t == DCN_LIST_BLIND ? sc.blind_coef : sc.nonmatch_coef);
     if (coef == 0.f) return;
-    coef *= grad_loss[0] / (float)num_pairs;
+    coef *= grad_loss[0] / denom;
     unsigned long long* gAp = accA + (int64_t)p * hw * D;
     unsigned long long* gBp = accB + (int64_t)p * hw * D;
 #pragma unroll
@@ -552,6 +592,19 @@ loss_bwd_saved_exact_kernel(int64_t hw, int D, int num_pairs, const int64_t* __r
             }
         }
     }
+}
+
+template <int LP, bool SINGLE>
+__global__ void __launch_bounds__(kThreads)
+loss_bwd_saved_exact_kernel(int64_t hw, int D, int num_pairs, const int64_t* __restrict__ idx_a,
+                            const int64_t* __restrict__ idx_b, const int64_t* __restrict__ offsets, dcn_loss_config cfg,
+                            const int* __restrict__ hard_neg, const float* __restrict__ grad_loss,
+                            const float* __restrict__ rec_d, const float* __restrict__ rec_s,
+                            const float* __restrict__ vmax, unsigned long long* __restrict__ accA,
+                            unsigned long long* __restrict__ accB) {
+    const int64_t beg = offsets[blockIdx.y], len = offsets[blockIdx.y + 1] - beg;
+    loss_bwd_saved_exact_body<LP, SINGLE>(hw, D, (float)num_pairs, idx_a, idx_b, offsets, cfg, beg, len, hard_neg, grad_loss, rec_d,
+                                          rec_s, vmax, accA, accB);
 }
 
 // grad = acc * 2^-e of the map's image pair; maps: [2][num_pairs][per_pair] (A maps, then B maps).  grid = (x, 2 * num_pairs):
@@ -582,6 +635,200 @@ loss_exact_convert_kernel(const long long* __restrict__ acc, const float* __rest
         for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < per_pair; i += (int64_t)gridDim.x * 256)
             dst[i] = bad ? nanv : (float)((double)src[i] * inv);
     }
+}
+
+// ------------------------------------------------------------------------------------------------ mixed data types
+// The same passes for a batch built on the device (include/dcn_hip.h section 1b): the offsets and one data type per image pair
+// are read from device memory only; the launches are shaped by host BOUNDS (no list longer than max_list_len, no pair with more
+// than max_pair_len entries, idx_a / idx_b hold `capacity` entries), every pair composes with the configuration of its own
+// type, and a pair that is left out -- type -1, an unknown type, offsets outside the bounds -- is a pair of empty lists to every
+// kernel: zero partials, zero rows, no gradient.  The partial layout and every reduction order are those of the one-type call,
+// so a batch of one type without empty pairs gives that call's bits (trailing zero partials change no fp64 sum).
+struct MixedTable {
+    dcn_loss_config cfg[DCN_LOSS_NUM_TYPES];
+};
+struct MixedLists {
+    const int64_t* offsets;        // device [4 * num_pairs + 1]
+    const int32_t* types;          // device [num_pairs]
+    int64_t max_list_len, max_pair_len, capacity;
+    int num_pairs;
+};
+constexpr int kPairSkip = 1 << 30;   // (internal, next to the DCN_LOSS_BAD_* bits)
+
+// kPairSkip and the reason (a DCN_LOSS_BAD_* bit; none for type -1) when pair p is left out, else 0.  A pair that passes has
+// its four lists inside [0, capacity), in order, each within max_list_len: nothing of it is read out of bounds.
+__device__ __forceinline__ int pair_skip(const MixedLists& m, int p, int& type) {
+    type = m.types[p];
+    if (type == -1) return kPairSkip;
+    if (type < 0 || type >= DCN_LOSS_NUM_TYPES) return kPairSkip | DCN_LOSS_BAD_TYPE;
+    const int64_t* o = m.offsets + 4 * p;
+    const int64_t o0 = o[0], o4 = o[4];
+    bool bad = o0 < 0 || o4 > m.capacity || o4 - o0 > m.max_pair_len;
+#pragma unroll
+    for (int t = 0; t < 4; ++t) {
+        const int64_t l = o[t + 1] - o[t];
+        bad |= l < 0 || l > m.max_list_len;
+    }
+    return bad ? (kPairSkip | DCN_LOSS_BAD_BOUNDS) : 0;
+}
+
+// pair_skip plus the layout check of the pixel-distance weights (a whole number of non-matches per match): finalize only
+__device__ __forceinline__ int pair_status(const MixedLists& m, const MixedTable& tab, int p, int& type) {
+    int st = pair_skip(m, p, type);
+    if (st & kPairSkip) return st;
+    const dcn_loss_config& cfg = tab.cfg[type];
+    const int64_t* o = m.offsets + 4 * p;
+    const int64_t mlen = o[1] - o[0];
+    for (int t = DCN_LIST_MASKED; t <= DCN_LIST_BACKGROUND; ++t) {
+        if (!cfg.pixel_weight[t]) continue;
+        const int64_t l = o[t + 1] - o[t];
+        if (mlen > 0 ? (l % mlen) != 0 : l != 0) st |= DCN_LOSS_BAD_PIXEL_LAYOUT;
+    }
+    return st;
+}
+
+__device__ __forceinline__ float valid_pairs(const int* __restrict__ num_valid) {
+    const int v = num_valid[0];
+    return (float)(v > 1 ? v : 1);
+}
+
+// grid = (chunks of max_list_len, 4*num_pairs)
+template <int LP, bool SINGLE>
+__global__ void __launch_bounds__(kThreads)
+loss_fwd_mixed_kernel(const float* __restrict__ A, const float* __restrict__ B, int64_t hw, int D,
+                      const int64_t* __restrict__ idx_a, const int64_t* __restrict__ idx_b, MixedLists m, MixedTable tab,
+                      double* __restrict__ part_sum, int* __restrict__ part_cnt, int* __restrict__ part_oob,
+                      float* __restrict__ rec_d, float* __restrict__ rec_s) {
+    int type;
+    const bool skip = pair_skip(m, blockIdx.y >> 2, type) != 0;
+    const int64_t beg = skip ? 0 : m.offsets[blockIdx.y], len = skip ? 0 : m.offsets[blockIdx.y + 1] - beg;
+    loss_fwd_body<LP, SINGLE>(A, B, hw, D, idx_a, idx_b, m.offsets, tab.cfg[skip ? 0 : type], beg, len, part_sum, part_cnt,
+                              nullptr, part_oob, rec_d, rec_s);
+}
+
+__device__ __forceinline__ void zero_pair(int p, float* __restrict__ terms, float* __restrict__ sums, int* __restrict__ hard_neg,
+                                          double* __restrict__ pair_loss) {
+    for (int k = 0; k < 5; ++k) terms[5 * p + k] = 0.f;
+    for (int t = 0; t < 4; ++t) { sums[4 * p + t] = 0.f; hard_neg[4 * p + t] = 0; }
+    pair_loss[p] = 0.0;
+}
+
+// few pairs: loss_finalize_all_kernel with a configuration per pair; loss = sum over the pairs kept / max(their number, 1)
+__global__ void __launch_bounds__(kThreads)
+loss_finalize_all_mixed_kernel(const double* __restrict__ part_sum, const int* __restrict__ part_cnt,
+                               const int* __restrict__ part_oob, int chunks, MixedLists m, MixedTable tab,
+                               float* __restrict__ terms, float* __restrict__ sums, int* __restrict__ hard_neg,
+                               double* __restrict__ pair_loss, float* __restrict__ loss, int* __restrict__ num_valid,
+                               int* __restrict__ status) {
+    __shared__ double s_S[8][4];
+    __shared__ int s_h[8][4];
+    __shared__ int s_o[8][4];
+    __shared__ int s_st[8];
+    reduce_all_partials(part_sum, part_cnt, part_oob, chunks, m.num_pairs, s_S, s_h, s_o);
+    if ((int)threadIdx.x < m.num_pairs) {
+        const int p = threadIdx.x;
+        int type;
+        const int st = pair_status(m, tab, p, type);
+        s_st[p] = st;
+        if (st & kPairSkip) zero_pair(p, terms, sums, hard_neg, pair_loss);
+        else compose_pair(p, s_S[p], s_h[p], m.offsets, tab.cfg[type], terms, sums, hard_neg, pair_loss);
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double total = 0.0;
+        int bits = m.offsets[4 * m.num_pairs] > m.capacity ? DCN_LOSS_BAD_BOUNDS : 0, valid = 0;
+        for (int p = 0; p < m.num_pairs; ++p) {
+            bits |= s_st[p] & ~kPairSkip;
+            if (s_st[p] & kPairSkip) continue;
+            total += pair_loss[p];
+            ++valid;
+            if (s_o[p][0] | s_o[p][1] | s_o[p][2] | s_o[p][3]) bits |= DCN_LOSS_BAD_INDEX;
+        }
+        loss[0] = (float)(total / (double)(valid > 1 ? valid : 1));
+        num_valid[0] = valid;
+        status[0] = bits;
+    }
+}
+
+// many pairs: one workgroup per pair (pair_flags[p] = its status bits and kPairSkip), then loss_mean_mixed_kernel
+__global__ void __launch_bounds__(kThreads)
+loss_finalize_mixed_kernel(const double* __restrict__ part_sum, const int* __restrict__ part_cnt, const int* __restrict__ part_oob,
+                           int chunks, MixedLists m, MixedTable tab, float* __restrict__ terms, float* __restrict__ sums,
+                           int* __restrict__ hard_neg, double* __restrict__ pair_loss, int* __restrict__ pair_flags) {
+    __shared__ double s_sum[kThreads / dcn::kWave];
+    __shared__ int s_cnt[kThreads / dcn::kWave];
+    __shared__ double s_S[4];
+    __shared__ int s_h[4];
+    const int p = blockIdx.x;
+    int type;
+    const int st = pair_status(m, tab, p, type);      // (the same value in every work-item)
+    if (st & kPairSkip) {
+        if (threadIdx.x == 0) {
+            zero_pair(p, terms, sums, hard_neg, pair_loss);
+            pair_flags[p] = st;
+        }
+        return;
+    }
+    const int o = finalize_pair(p, part_sum, part_cnt, part_oob, chunks, m.offsets, tab.cfg[type], terms, sums, hard_neg, pair_loss,
+                                s_sum, s_cnt, s_S, s_h);
+    if (threadIdx.x == 0) pair_flags[p] = st | (o ? DCN_LOSS_BAD_INDEX : 0);
+}
+
+__global__ void __launch_bounds__(64)
+loss_mean_mixed_kernel(const double* __restrict__ pair_loss, const int* __restrict__ pair_flags, MixedLists m,
+                       float* __restrict__ loss, int* __restrict__ num_valid, int* __restrict__ status) {
+    if (threadIdx.x != 0) return;
+    double total = 0.0;
+    int bits = m.offsets[4 * m.num_pairs] > m.capacity ? DCN_LOSS_BAD_BOUNDS : 0, valid = 0;
+    for (int p = 0; p < m.num_pairs; ++p) {           // pair order: deterministic
+        bits |= pair_flags[p] & ~kPairSkip;
+        if (pair_flags[p] & kPairSkip) continue;
+        total += pair_loss[p];
+        ++valid;
+    }
+    loss[0] = (float)(total / (double)(valid > 1 ? valid : 1));
+    num_valid[0] = valid;
+    status[0] = bits;
+}
+
+template <int LP, bool SINGLE>
+__global__ void __launch_bounds__(kThreads)
+loss_bwd_saved_mixed_kernel(int64_t hw, int D, const int64_t* __restrict__ idx_a, const int64_t* __restrict__ idx_b, MixedLists m,
+                            MixedTable tab, const int* __restrict__ hard_neg, const int* __restrict__ num_valid,
+                            const float* __restrict__ grad_loss, const float* __restrict__ rec_d,
+                            const float* __restrict__ rec_s, float* __restrict__ gA, float* __restrict__ gB) {
+    int type;
+    if (pair_skip(m, blockIdx.y >> 2, type)) return;
+    const int64_t beg = m.offsets[blockIdx.y], len = m.offsets[blockIdx.y + 1] - beg;
+    loss_bwd_saved_body<LP, SINGLE>(hw, D, valid_pairs(num_valid), idx_a, idx_b, m.offsets, tab.cfg[type], beg, len, hard_neg,
+                                    grad_loss, rec_d, rec_s, gA, gB);
+}
+
+template <int LP, bool SINGLE>
+__global__ void __launch_bounds__(kThreads)
+loss_bwd_vmax_mixed_kernel(int D, MixedLists m, MixedTable tab, const int* __restrict__ hard_neg,
+                           const int* __restrict__ num_valid, const float* __restrict__ grad_loss,
+                           const float* __restrict__ rec_d, const float* __restrict__ rec_s, unsigned* __restrict__ vmax_bits) {
+    int type;
+    if (pair_skip(m, blockIdx.y >> 2, type)) return;
+    const int64_t beg = m.offsets[blockIdx.y], len = m.offsets[blockIdx.y + 1] - beg;
+    loss_bwd_vmax_body<LP, SINGLE>(D, valid_pairs(num_valid), m.offsets, tab.cfg[type], beg, len, hard_neg, grad_loss, rec_d, rec_s,
+                                   vmax_bits);
+}
+
+template <int LP, bool SINGLE>
+__global__ void __launch_bounds__(kThreads)
+loss_bwd_saved_exact_mixed_kernel(int64_t hw, int D, const int64_t* __restrict__ idx_a, const int64_t* __restrict__ idx_b,
+                                  MixedLists m, MixedTable tab, const int* __restrict__ hard_neg,
+                                  const int* __restrict__ num_valid, const float* __restrict__ grad_loss,
+                                  const float* __restrict__ rec_d, const float* __restrict__ rec_s,
+                                  const float* __restrict__ vmax, unsigned long long* __restrict__ accA,
+                                  unsigned long long* __restrict__ accB) {
+    int type;
+    if (pair_skip(m, blockIdx.y >> 2, type)) return;
+    const int64_t beg = m.offsets[blockIdx.y], len = m.offsets[blockIdx.y + 1] - beg;
+    loss_bwd_saved_exact_body<LP, SINGLE>(hw, D, valid_pairs(num_valid), idx_a, idx_b, m.offsets, tab.cfg[type], beg, len, hard_neg,
+                                          grad_loss, rec_d, rec_s, vmax, accA, accB);
 }
 
 // workgroups per list for descriptor dimension d (d <= 0: the worst case over all d, for workspace sizing)
@@ -914,6 +1161,172 @@ extern "C" int dcn_contrastive_loss_backward_saved_exact(int num_pairs, int64_t 
                 break;
         }
 #undef DCN_LAUNCH_BWDX
+    }
+    const unsigned bx = (unsigned)std::max<int64_t>(1, std::min<int64_t>(dcn::ceil_div64((int64_t)per_pair / 2 + 1, 256 * 4),
+                                                                         (256 * 16) / (2 * num_pairs) + 1));
+    hipLaunchKernelGGL(loss_exact_convert_kernel, dim3(bx, 2 * num_pairs), dim3(256), 0, st, (const long long*)workspace,
+                       (const float*)vmax, grad_a, grad_b, (int64_t)per_pair, num_pairs);
+    return dcn::check_launch();
+}
+
+// ------------------------------------------------------------------------------------------------ mixed data types: entry points
+namespace {
+// the argument checks the three mixed entry points share; fills the kernels' two argument blocks
+int mixed_args(int num_pairs, int64_t hw, int d, const int64_t* idx_a, const int64_t* idx_b, const int64_t* offsets_dev,
+               const int32_t* types_dev, const dcn_loss_config* cfgs, int64_t max_list_len, int64_t max_pair_len,
+               int64_t capacity, MixedLists* m, MixedTable* tab) {
+    if (!offsets_dev || !types_dev || !cfgs || num_pairs < 1 || hw < 1 || d < 1 || max_list_len < 0 || max_pair_len < 0 ||
+        capacity < 0)
+        return DCN_E_INVALID;
+    if (capacity > 0 && (!idx_a || !idx_b)) return DCN_E_INVALID;
+    if (num_pairs > 16383) return DCN_E_UNSUPPORTED;                  // (grid.y of every launch: 4 per pair)
+    m->offsets = offsets_dev;
+    m->types = types_dev;
+    m->max_list_len = max_list_len < capacity ? max_list_len : capacity;
+    m->max_pair_len = max_pair_len < capacity ? max_pair_len : capacity;
+    m->capacity = capacity;
+    m->num_pairs = num_pairs;
+    for (int t = 0; t < DCN_LOSS_NUM_TYPES; ++t) tab->cfg[t] = cfgs[t];
+    return DCN_OK;
+}
+}  // namespace
+
+extern "C" int dcn_contrastive_loss_mixed_forward(const float* desc_a, const float* desc_b, int num_pairs, int64_t hw, int d,
+                                                  const int64_t* idx_a, const int64_t* idx_b, const int64_t* offsets_dev,
+                                                  const int32_t* types_dev, const dcn_loss_config* cfgs, int64_t max_list_len,
+                                                  int64_t max_pair_len, int64_t capacity, float* terms, float* sums,
+                                                  int32_t* hard_neg, float* loss, int32_t* num_valid, int32_t* status,
+                                                  void* workspace, float* pair_records, void* stream) {
+    MixedLists m;
+    MixedTable tab;
+    const int rc = mixed_args(num_pairs, hw, d, idx_a, idx_b, offsets_dev, types_dev, cfgs, max_list_len, max_pair_len, capacity,
+                              &m, &tab);
+    if (rc != DCN_OK) return rc;
+    if (!desc_a || !desc_b || !terms || !sums || !hard_neg || !loss || !num_valid || !status || !workspace) return DCN_E_INVALID;
+    hipStream_t st = (hipStream_t)stream;
+    const int chunks = chunks_for(m.max_list_len, d);
+    const size_t n = (size_t)4 * num_pairs * chunks;
+    double* part_sum = (double*)workspace;                           // (the layout of loss_forward_impl)
+    double* pair_loss = part_sum + n;
+    int* part_cnt = (int*)(pair_loss + num_pairs);
+    int* part_oob = part_cnt + n;
+    int* pair_flags = part_oob + n;
+    float* rec_d = pair_records;
+    float* rec_s = pair_records ? pair_records + (size_t)capacity * d : nullptr;
+    const dim3 grid(chunks, 4 * num_pairs), block(kThreads);
+#define DCN_LAUNCH_FWDM(LP, SINGLE)                                                                                        \
+    hipLaunchKernelGGL((loss_fwd_mixed_kernel<LP, SINGLE>), grid, block, 0, st, desc_a, desc_b, hw, d, idx_a, idx_b, m, tab, \
+                       part_sum, part_cnt, part_oob, rec_d, rec_s)
+    switch (lanes_per_pair(d)) {
+        case 4: DCN_LAUNCH_FWDM(4, true); break;
+        case 8: DCN_LAUNCH_FWDM(8, true); break;
+        case 16: DCN_LAUNCH_FWDM(16, true); break;
+        default:
+            if (d <= 32) DCN_LAUNCH_FWDM(32, true);
+            else DCN_LAUNCH_FWDM(32, false);
+            break;
+    }
+#undef DCN_LAUNCH_FWDM
+    if (num_pairs <= 8) {
+        hipLaunchKernelGGL(loss_finalize_all_mixed_kernel, dim3(1), block, 0, st, part_sum, part_cnt, part_oob, chunks, m, tab,
+                           terms, sums, (int*)hard_neg, pair_loss, loss, (int*)num_valid, (int*)status);
+    } else {
+        hipLaunchKernelGGL(loss_finalize_mixed_kernel, dim3(num_pairs), block, 0, st, part_sum, part_cnt, part_oob, chunks, m, tab,
+                           terms, sums, (int*)hard_neg, pair_loss, pair_flags);
+        hipLaunchKernelGGL(loss_mean_mixed_kernel, dim3(1), dim3(64), 0, st, (const double*)pair_loss, (const int*)pair_flags, m,
+                           loss, (int*)num_valid, (int*)status);
+    }
+    return dcn::check_launch();
+}
+
+extern "C" int dcn_contrastive_loss_mixed_backward_saved(int num_pairs, int64_t hw, int d, const int64_t* idx_a,
+                                                         const int64_t* idx_b, const int64_t* offsets_dev,
+                                                         const int32_t* types_dev, const dcn_loss_config* cfgs,
+                                                         int64_t max_list_len, int64_t max_pair_len, int64_t capacity,
+                                                         const int32_t* hard_neg, const int32_t* num_valid,
+                                                         const float* grad_loss, const float* pair_records, int prefilled,
+                                                         float* grad_a, float* grad_b, void* stream) {
+    MixedLists m;
+    MixedTable tab;
+    const int rc = mixed_args(num_pairs, hw, d, idx_a, idx_b, offsets_dev, types_dev, cfgs, max_list_len, max_pair_len, capacity,
+                              &m, &tab);
+    if (rc != DCN_OK) return rc;
+    if (!hard_neg || !num_valid || !grad_loss || !grad_a || !grad_b) return DCN_E_INVALID;
+    hipStream_t st = (hipStream_t)stream;
+    const size_t bytes = (size_t)num_pairs * (size_t)hw * (size_t)d * sizeof(float);
+    if (!prefilled) {
+        if ((char*)grad_b == (char*)grad_a + bytes) {
+            if (dcn::fill_bytes_async(grad_a, 0, 2 * bytes, st) != DCN_OK) return DCN_E_LAUNCH;
+        } else {
+            if (dcn::fill_bytes_async(grad_a, 0, bytes, st) != DCN_OK) return DCN_E_LAUNCH;
+            if (dcn::fill_bytes_async(grad_b, 0, bytes, st) != DCN_OK) return DCN_E_LAUNCH;
+        }
+    }
+    if (m.max_list_len == 0) return DCN_OK;
+    if (!pair_records) return DCN_E_INVALID;
+    const float* rec_d = pair_records;
+    const float* rec_s = pair_records + (size_t)capacity * d;
+    const dim3 grid(chunks_for(m.max_list_len, d), 4 * num_pairs), block(kThreads);
+#define DCN_LAUNCH_BWDSM(LP, SINGLE)                                                                                          \
+    hipLaunchKernelGGL((loss_bwd_saved_mixed_kernel<LP, SINGLE>), grid, block, 0, st, hw, d, idx_a, idx_b, m, tab,             \
+                       (const int*)hard_neg, (const int*)num_valid, grad_loss, rec_d, rec_s, grad_a, grad_b)
+    switch (lanes_per_pair(d)) {
+        case 4: DCN_LAUNCH_BWDSM(4, true); break;
+        case 8: DCN_LAUNCH_BWDSM(8, true); break;
+        case 16: DCN_LAUNCH_BWDSM(16, true); break;
+        default:
+            if (d <= 32) DCN_LAUNCH_BWDSM(32, true);
+            else DCN_LAUNCH_BWDSM(32, false);
+            break;
+    }
+#undef DCN_LAUNCH_BWDSM
+    return dcn::check_launch();
+}
+
+extern "C" int dcn_contrastive_loss_mixed_backward_saved_exact(int num_pairs, int64_t hw, int d, const int64_t* idx_a,
+                                                               const int64_t* idx_b, const int64_t* offsets_dev,
+                                                               const int32_t* types_dev, const dcn_loss_config* cfgs,
+                                                               int64_t max_list_len, int64_t max_pair_len, int64_t capacity,
+                                                               const int32_t* hard_neg, const int32_t* num_valid,
+                                                               const float* grad_loss, const float* pair_records,
+                                                               void* workspace, float* grad_a, float* grad_b, void* stream) {
+    MixedLists m;
+    MixedTable tab;
+    const int rc = mixed_args(num_pairs, hw, d, idx_a, idx_b, offsets_dev, types_dev, cfgs, max_list_len, max_pair_len, capacity,
+                              &m, &tab);
+    if (rc != DCN_OK) return rc;
+    if (!hard_neg || !num_valid || !grad_loss || !workspace || !grad_a || !grad_b) return DCN_E_INVALID;
+    // the headroom of the 63-bit sums, from the host bound: the kernels leave out any pair with more entries than that
+    if (m.max_pair_len >= ((int64_t)1 << 22)) return DCN_E_UNSUPPORTED;
+    hipStream_t st = (hipStream_t)stream;
+    const size_t per_pair = (size_t)hw * d, map_bytes = (size_t)num_pairs * per_pair * sizeof(long long);
+    unsigned long long* accA = (unsigned long long*)workspace;
+    unsigned long long* accB = accA + (size_t)num_pairs * per_pair;
+    float* vmax = (float*)((char*)workspace + 2 * map_bytes);
+    if (dcn::fill_bytes_async(workspace, 0, dcn_loss_exact_workspace_bytes(num_pairs, hw, d), st) != DCN_OK) return DCN_E_LAUNCH;
+    if (m.max_list_len > 0) {
+        if (!pair_records) return DCN_E_INVALID;
+        const float* rec_d = pair_records;
+        const float* rec_s = pair_records + (size_t)capacity * d;
+        const dim3 grid(chunks_for(m.max_list_len, d), 4 * num_pairs), block(kThreads);
+#define DCN_LAUNCH_BWDXM(LP, SINGLE)                                                                                          \
+        do {                                                                                                                  \
+            hipLaunchKernelGGL((loss_bwd_vmax_mixed_kernel<LP, SINGLE>), grid, block, 0, st, d, m, tab, (const int*)hard_neg,  \
+                               (const int*)num_valid, grad_loss, rec_d, rec_s, (unsigned*)vmax);                              \
+            hipLaunchKernelGGL((loss_bwd_saved_exact_mixed_kernel<LP, SINGLE>), grid, block, 0, st, hw, d, idx_a, idx_b, m, tab, \
+                               (const int*)hard_neg, (const int*)num_valid, grad_loss, rec_d, rec_s, (const float*)vmax, accA, \
+                               accB);                                                                                         \
+        } while (0)
+        switch (lanes_per_pair(d)) {
+            case 4: DCN_LAUNCH_BWDXM(4, true); break;
+            case 8: DCN_LAUNCH_BWDXM(8, true); break;
+            case 16: DCN_LAUNCH_BWDXM(16, true); break;
+            default:
+                if (d <= 32) DCN_LAUNCH_BWDXM(32, true);
+                else DCN_LAUNCH_BWDXM(32, false);
+                break;
+        }
+#undef DCN_LAUNCH_BWDXM
     }
     const unsigned bx = (unsigned)std::max<int64_t>(1, std::min<int64_t>(dcn::ceil_div64((int64_t)per_pair / 2 + 1, 256 * 4),
                                                                          (256 * 16) / (2 * num_pairs) + 1));

@@ -746,3 +746,169 @@ extern "C" int dcn_across_scene_samples(int n, int h, int w, const uint8_t* mask
     write_out(o, st);
     return dcn::check_launch();
 }
+
+// ------------------------------------------------------------------------------------------------ joining sample batches
+// dcn_concat_samples: the outputs of up to kMaxGroups calls above as ONE batch -- pairs in the order given, lists compacted.
+//   concat_offsets_kernel   one workgroup: checks every group's offsets (from 0, increasing, within its capacity), shifts them
+//                           by the entries of the groups in front, ORs the status words.
+//   concat_write_kernel     write_kernel's pass over the output capacity: each work-item owns 4 consecutive entries, finds its
+//                           (pair, list, entry) by a binary search over the joined offsets held in LDS, copies the entry from
+//                           the pair's group (16-byte stores) and writes -1 past offsets[4n].
+namespace {
+
+constexpr int kMaxGroups = DCN_CONCAT_MAX_GROUPS;
+
+struct ConcatArgs {
+    const int64_t* src_a[kMaxGroups];
+    const int64_t* src_b[kMaxGroups];
+    const int64_t* src_off[kMaxGroups];        // [4 * n_g + 1]
+    const int32_t* src_status[kMaxGroups];     // [1] or null
+    int64_t src_cap[kMaxGroups];
+    int base[kMaxGroups + 1];                  // first output pair of group g; base[groups] = n
+    int groups, n;
+    int64_t* idx_a;                            // [cap]
+    int64_t* idx_b;
+    int64_t* offsets;                          // [4n + 1]
+    int32_t* status;
+    int64_t cap;
+};
+
+__global__ void __launch_bounds__(1024) concat_offsets_kernel(ConcatArgs a) {
+    __shared__ int bad[kMaxGroups];
+    __shared__ int64_t shift[kMaxGroups + 1];
+    if (threadIdx.x < kMaxGroups) bad[threadIdx.x] = 0;
+    __syncthreads();
+#pragma unroll
+    for (int g = 0; g < kMaxGroups; ++g) {
+        if (g >= a.groups) break;
+        const int64_t* o = a.src_off[g];
+        const int nl = 4 * (a.base[g + 1] - a.base[g]);
+        int b = 0;
+        for (int i = threadIdx.x; i < nl; i += 1024) b |= o[i + 1] < o[i];
+        if (threadIdx.x == 0) b |= o[0] != 0 || o[nl] > a.src_cap[g];
+        if (b) bad[g] = 1;                      // (racing writes of the same value)
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        int st = 0;
+        int64_t pos = 0;
+#pragma unroll
+        for (int g = 0; g < kMaxGroups; ++g) {
+            if (g >= a.groups) break;
+            shift[g] = pos;
+            if (bad[g]) st |= DCN_SAMPLE_BAD_OFFSETS;          // the group's pairs keep their slots, with empty lists
+            else pos += a.src_off[g][4 * (a.base[g + 1] - a.base[g])];
+            if (a.src_status[g]) st |= a.src_status[g][0];
+        }
+        if (pos > a.cap) st |= DCN_SAMPLE_BAD_OFFSETS;
+        a.offsets[4 * a.n] = pos;
+        a.status[0] = st;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int g = 0; g < kMaxGroups; ++g) {
+        if (g >= a.groups) break;
+        const int64_t* o = a.src_off[g];
+        const int nl = 4 * (a.base[g + 1] - a.base[g]);
+        int64_t* out = a.offsets + 4 * a.base[g];
+        for (int i = threadIdx.x; i < nl; i += 1024) out[i] = shift[g] + (bad[g] ? 0 : o[i]);
+    }
+}
+
+__global__ void __launch_bounds__(kThreads) concat_write_kernel(ConcatArgs a) {
+    __shared__ int64_t off[4 * kMaxPairs + 1];
+    __shared__ const int64_t* sa[kMaxGroups];
+    __shared__ const int64_t* sb[kMaxGroups];
+    __shared__ int base[kMaxGroups + 1];
+    const int nl = 4 * a.n;
+    for (int i = threadIdx.x; i <= nl; i += kThreads) off[i] = a.offsets[i];
+    if (threadIdx.x == 0) {
+#pragma unroll
+        for (int g = 0; g < kMaxGroups; ++g) {
+            sa[g] = a.src_a[g];
+            sb[g] = a.src_b[g];
+            base[g] = a.base[g];                                // (= n from the last group on)
+        }
+        base[kMaxGroups] = a.n;
+    }
+    __syncthreads();
+    const int64_t total = off[nl] < a.cap ? off[nl] : a.cap;
+    for (int64_t i0 = ((int64_t)blockIdx.x * kThreads + threadIdx.x) * kRun; i0 < a.cap;
+         i0 += (int64_t)gridDim.x * kThreads * kRun) {
+        int64_t va[kRun], vb[kRun];
+        int l = 0, g = 0;
+        if (i0 < total) {
+            int lo = 0, hi = nl - 1;
+            while (lo < hi) {
+                const int mid = (lo + hi + 1) >> 1;
+                if (off[mid] <= i0) lo = mid; else hi = mid - 1;
+            }
+            l = lo;
+        }
+#pragma unroll
+        for (int r = 0; r < kRun; ++r) {
+            const int64_t i = i0 + r;
+            va[r] = vb[r] = -1;
+            if (i < total) {
+                while (off[l + 1] <= i) ++l;                    // entry i - off[l] of list l & 3 of pair l >> 2
+                while (base[g + 1] <= (l >> 2)) ++g;            // ... which is entry i - off[4 * base[g]] of its group's lists
+                const int64_t e = i - off[4 * base[g]];
+                va[r] = sa[g][e];
+                vb[r] = sb[g][e];
+            }
+        }
+        if (i0 + kRun <= a.cap) {
+            int64_t* pa = a.idx_a + i0;
+            int64_t* pb = a.idx_b + i0;
+            *reinterpret_cast<I64x2*>(pa) = I64x2{va[0], va[1]};
+            *reinterpret_cast<I64x2*>(pa + 2) = I64x2{va[2], va[3]};
+            *reinterpret_cast<I64x2*>(pb) = I64x2{vb[0], vb[1]};
+            *reinterpret_cast<I64x2*>(pb + 2) = I64x2{vb[2], vb[3]};
+        } else {
+            for (int r = 0; r < kRun && i0 + r < a.cap; ++r) {
+                a.idx_a[i0 + r] = va[r];
+                a.idx_b[i0 + r] = vb[r];
+            }
+        }
+    }
+}
+
+}  // namespace
+
+extern "C" int dcn_concat_samples(int groups, const int* n, const int64_t* const* idx_a, const int64_t* const* idx_b,
+                                  const int64_t* const* offsets, const int64_t* capacity_in, const int32_t* const* status_in,
+                                  int64_t* idx_a_out, int64_t* idx_b_out, int64_t capacity, int64_t* offsets_out,
+                                  int32_t* status, void* stream) {
+    if (groups < 1 || groups > kMaxGroups || !n || !idx_a || !idx_b || !offsets || !capacity_in || !offsets_out || !status ||
+        capacity < 0 || (capacity > 0 && (!idx_a_out || !idx_b_out)) || !aligned16(idx_a_out) || !aligned16(idx_b_out))
+        return DCN_E_INVALID;
+    ConcatArgs a;
+    int total = 0;
+    for (int g = 0; g < kMaxGroups; ++g) {
+        const bool on = g < groups;
+        if (on && (n[g] < 1 || !offsets[g] || capacity_in[g] < 0 || (capacity_in[g] > 0 && (!idx_a[g] || !idx_b[g]))))
+            return DCN_E_INVALID;
+        a.src_a[g] = on ? idx_a[g] : nullptr;
+        a.src_b[g] = on ? idx_b[g] : nullptr;
+        a.src_off[g] = on ? offsets[g] : nullptr;
+        a.src_status[g] = on && status_in ? status_in[g] : nullptr;
+        a.src_cap[g] = on ? capacity_in[g] : 0;
+        a.base[g] = total;
+        if (on) total += n[g];
+        if (total > kMaxPairs) return DCN_E_INVALID;
+    }
+    a.base[kMaxGroups] = total;
+    a.groups = groups;
+    a.n = total;
+    a.idx_a = idx_a_out;
+    a.idx_b = idx_b_out;
+    a.offsets = offsets_out;
+    a.status = status;
+    a.cap = capacity;
+    hipStream_t st = (hipStream_t)stream;
+    hipLaunchKernelGGL(concat_offsets_kernel, dim3(1), dim3(1024), 0, st, a);
+    int64_t blocks = dcn::ceil_div64(dcn::ceil_div64(capacity, kRun), kThreads);
+    blocks = blocks < 1 ? 1 : (blocks > 2048 ? 2048 : blocks);
+    hipLaunchKernelGGL(concat_write_kernel, dim3((unsigned)blocks), dim3(kThreads), 0, st, a);
+    return dcn::check_launch();
+}

@@ -73,6 +73,14 @@ SYMBOLS = {
     "dcn_contrastive_loss_backward_saved_exact": (c_int, [c_int, c_int64, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
                                                           ctypes.POINTER(LossConfig), c_void_p, c_void_p, c_void_p, c_void_p,
                                                           c_void_p, c_void_p, c_void_p]),
+    "dcn_contrastive_loss_mixed_forward": (c_int, [c_void_p, c_void_p, c_int, c_int64, c_int] + [c_void_p] * 4
+                                           + [ctypes.POINTER(LossConfig), c_int64, c_int64, c_int64] + [c_void_p] * 9),
+    "dcn_contrastive_loss_mixed_backward_saved": (c_int, [c_int, c_int64, c_int] + [c_void_p] * 4
+                                                  + [ctypes.POINTER(LossConfig), c_int64, c_int64, c_int64] + [c_void_p] * 4
+                                                  + [c_int, c_void_p, c_void_p, c_void_p]),
+    "dcn_contrastive_loss_mixed_backward_saved_exact": (c_int, [c_int, c_int64, c_int] + [c_void_p] * 4
+                                                        + [ctypes.POINTER(LossConfig), c_int64, c_int64, c_int64]
+                                                        + [c_void_p] * 8),
     "dcn_fill_bytes": (c_int, [c_void_p, c_int, c_size_t, c_void_p]),
     "dcn_plan_create": (c_int, [c_char_p, c_int, c_int, c_int, c_int, c_int, ctypes.POINTER(c_void_p)]),
     "dcn_plan_destroy": (None, [c_void_p]),
@@ -196,6 +204,7 @@ SYMBOLS = {
                              + [c_int, c_void_p, c_void_p, c_int64] + [c_void_p] * 6),
     "dcn_across_scene_samples": (c_int, [c_int, c_int, c_int, c_void_p, c_void_p, c_int64] + [c_void_p] * 4
                                  + [c_int, c_void_p, c_void_p, c_int64] + [c_void_p] * 6),
+    "dcn_concat_samples": (c_int, [c_int] + [c_void_p] * 8 + [c_int64, c_void_p, c_void_p, c_void_p]),
     "dcn_merge_prune": (c_int, [c_int, c_int, c_int] + [c_void_p] * 10 + [c_int64] + [c_void_p] * 5 + [c_int64, c_int]
                         + [c_void_p] * 9),
     "dcn_select_frames": (c_int, [c_int, c_int, ctypes.POINTER(FrameStoreDesc), c_int, ctypes.c_double, ctypes.c_double]

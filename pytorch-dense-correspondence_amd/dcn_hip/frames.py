@@ -17,8 +17,8 @@ import torch
 
 from . import _lib
 from .samples import (CAM_FLOATS, DIFFERENT_OBJECT, MULTI_OBJECT, SINGLE_OBJECT_ACROSS_SCENE, SINGLE_OBJECT_WITHIN_SCENE,
-                      SYNTHETIC_MULTI_OBJECT, _f32, build_across_scene_samples, build_within_scene_samples, draw_seeds,
-                      options_from_config)
+                      SYNTHETIC_MULTI_OBJECT, _f32, build_across_scene_samples, build_within_scene_samples,
+                      concat_sample_batches, draw_seeds, options_from_config)
 
 BAD_INDEX, BAD_DRAWS, NO_CANDIDATES = 1, 2, 4
 SLOTS = 4
@@ -288,13 +288,33 @@ def data_type_distribution(training_config):
     return types, ps
 
 
-def draw_training_batch(store, batch_size, training_config, *, generator=None, host_rng=None):
+def _build_samples(fb, dt, o, generator):
+    if dt in (SINGLE_OBJECT_WITHIN_SCENE, MULTI_OBJECT):
+        return build_within_scene_samples(fb.depth[0], fb.depth[1], fb.mask[0], fb.mask[1], None, None, None, fb.rgb[0],
+                                          fb.rgb[1], num_matching_attempts=o.num_matching_attempts,
+                                          sample_matches_only_off_mask=o.sample_matches_only_off_mask,
+                                          num_masked_non_matches_per_match=o.num_masked_non_matches_per_match,
+                                          num_background_non_matches_per_match=o.num_background_non_matches_per_match,
+                                          use_image_b_mask_inv=o.use_image_b_mask_inv, domain_randomize=o.domain_randomize,
+                                          generator=generator, data_type=dt, cameras=fb.cams[0])
+    return build_across_scene_samples(fb.mask[0], fb.mask[1], fb.rgb[0], fb.rgb[1], num_samples=o.cross_scene_num_samples,
+                                      domain_randomize=o.domain_randomize, generator=generator, data_type=dt)
+
+
+def draw_training_batch(store, batch_size, training_config, *, generator=None, host_rng=None, per_pair_types=False):
     """One training batch from the store: the data type drawn on the host (``host_rng``: a numpy RandomState / Generator,
     default ``np.random``) from training.yaml's probabilities -- one type per batch, since the loss composes per call --
     then select_frames and build_within_scene_samples / build_across_scene_samples with options_from_config, all with
     ``generator``.  -> (SampleBatch, data_type, FrameBatch).  No host synchronization (SampleBatch.pair_lists() is the one
     read).  SYNTHETIC_MULTI_OBJECT (select_frames serves its four frames for merge.merge_synthetic_samples) is not chained
-    here: a probability > 0 for it raises NotImplementedError."""
+    here: a probability > 0 for it raises NotImplementedError.
+
+    ``per_pair_types=True``: one type per PAIR, as the reference's loader draws one per sample -- ``batch_size`` draws of
+    ``host_rng.choice`` in pair order; the pairs of each drawn type go through select_frames and their builder as one group
+    and the groups are joined (samples.concat_sample_batches) in ascending type order, so pair i of the batch has type
+    ``sorted(types_host)[i]`` (or -1 on the device when it came out empty).  -> (SampleBatch, types_host int array
+    [batch_size] in draw order, [FrameBatch per group]) for ``loss_composer.get_loss_mixed(..., sb.device_lists())``; no host
+    synchronization."""
     types, ps = data_type_distribution(training_config)
     if SYNTHETIC_MULTI_OBJECT in types:
         raise NotImplementedError("draw_training_batch does not build SYNTHETIC_MULTI_OBJECT samples: select its four frames "
@@ -302,18 +322,15 @@ def draw_training_batch(store, batch_size, training_config, *, generator=None, h
     for t in types:
         store.check_type(t)
     rng = host_rng if host_rng is not None else np.random
+    o = options_from_config(training_config)
+    if per_pair_types:
+        drawn = np.array([int(types[int(rng.choice(len(types), p=ps))]) for _ in range(int(batch_size))], dtype=np.int64)
+        groups, fbs = [], []
+        for dt in sorted(set(drawn.tolist())):
+            fb = select_frames(store, int(np.sum(drawn == dt)), dt, generator=generator)
+            fbs.append(fb)
+            groups.append(_build_samples(fb, dt, o, generator))
+        return concat_sample_batches(groups), drawn, fbs
     dt = int(types[int(rng.choice(len(types), p=ps))])
     fb = select_frames(store, batch_size, dt, generator=generator)
-    o = options_from_config(training_config)
-    if dt in (SINGLE_OBJECT_WITHIN_SCENE, MULTI_OBJECT):
-        sb = build_within_scene_samples(fb.depth[0], fb.depth[1], fb.mask[0], fb.mask[1], None, None, None, fb.rgb[0],
-                                        fb.rgb[1], num_matching_attempts=o.num_matching_attempts,
-                                        sample_matches_only_off_mask=o.sample_matches_only_off_mask,
-                                        num_masked_non_matches_per_match=o.num_masked_non_matches_per_match,
-                                        num_background_non_matches_per_match=o.num_background_non_matches_per_match,
-                                        use_image_b_mask_inv=o.use_image_b_mask_inv, domain_randomize=o.domain_randomize,
-                                        generator=generator, data_type=dt, cameras=fb.cams[0])
-    else:
-        sb = build_across_scene_samples(fb.mask[0], fb.mask[1], fb.rgb[0], fb.rgb[1], num_samples=o.cross_scene_num_samples,
-                                        domain_randomize=o.domain_randomize, generator=generator, data_type=dt)
-    return sb, dt, fb
+    return _build_samples(fb, dt, o, generator), dt, fb

@@ -238,6 +238,116 @@ class _ContrastiveLossFn(torch.autograd.Function):
         return ga, gb, None, None, None
 
 
+NUM_TYPES = 5                                          # SpartanDatasetDataType 0 .. 4; -1 on the device: pair left out
+BAD_INDEX, BAD_TYPE, BAD_BOUNDS, BAD_PIXEL_LAYOUT = 1, 2, 4, 8   # status bits of contrastive_loss_mixed
+
+
+class DeviceLists(object):
+    """Pair lists that never left the device (samples.SampleBatch.device_lists()): ``idx_a`` / ``idx_b`` int64 [capacity],
+    ``offsets`` int64 [4B + 1] and ``types`` int32 [B] (data type per pair, -1: leave the pair out) on the device, and the two
+    bounds the host knows without reading them: no list is longer than ``max_list_len``, no pair has more than
+    ``max_pair_len`` entries.  The kernels check both (status bit BAD_BOUNDS; such a pair is left out)."""
+
+    def __init__(self, idx_a, idx_b, offsets, types, max_list_len, max_pair_len):
+        if idx_a.dtype != torch.int64 or idx_b.dtype != torch.int64 or offsets.dtype != torch.int64 or types.dtype != torch.int32:
+            raise TypeError("DeviceLists: idx_a / idx_b / offsets must be int64, types int32")
+        if idx_a.numel() != idx_b.numel() or offsets.numel() != 4 * types.numel() + 1 or types.numel() < 1:
+            raise ValueError("DeviceLists: idx_a / idx_b of one length, offsets [4B + 1], types [B]")
+        self.idx_a = idx_a.contiguous().view(-1)
+        self.idx_b = idx_b.contiguous().view(-1)
+        self.offsets = offsets.contiguous().view(-1)
+        self.types = types.contiguous().view(-1)
+        self.num_pairs = int(types.numel())
+        self.capacity = int(idx_a.numel())
+        self.max_list_len = min(int(max_list_len), self.capacity)
+        self.max_pair_len = min(int(max_pair_len), self.capacity)
+        if self.max_list_len < 0 or self.max_pair_len < 0:
+            raise ValueError("DeviceLists: the bounds must be >= 0")
+
+
+def config_table(cfgs):
+    """The ``dcn_loss_config[5]`` of the mixed call from five ``make_config`` results, indexed by data type."""
+    if len(cfgs) != NUM_TYPES:
+        raise ValueError("one loss configuration per data type (%d), got %d" % (NUM_TYPES, len(cfgs)))
+    table = (_lib.LossConfig * NUM_TYPES)()
+    for i, c in enumerate(cfgs):
+        table[i] = c
+    return table
+
+
+class _MixedLossFn(torch.autograd.Function):
+    """contrastive_loss_mixed: _ContrastiveLossFn for DeviceLists.  Every size used here is a host bound; nothing is read back."""
+
+    @staticmethod
+    def forward(ctx, desc_a, desc_b, lists, table):
+        lib = _lib.get()
+        _lib.require_device(desc_a, desc_b, lists.idx_a, lists.idx_b, lists.offsets, lists.types)
+        if desc_a.dtype != torch.float32 or desc_b.dtype != torch.float32:
+            raise TypeError("dcn_hip loss kernels take float32 descriptor maps, got %s / %s (cast with .float(); the gradient "
+                            "then flows back through the cast)" % (desc_a.dtype, desc_b.dtype))
+        if desc_a.dim() != 3 or desc_b.shape != desc_a.shape or int(desc_a.shape[0]) != lists.num_pairs:
+            raise ValueError("descriptor maps %s / %s do not match %d pair lists" %
+                             (tuple(desc_a.shape), tuple(desc_b.shape), lists.num_pairs))
+        desc_a, desc_b = desc_a.contiguous(), desc_b.contiguous()
+        P, HW, D = (int(x) for x in desc_a.shape)
+        dev = desc_a.device
+        f32 = dict(dtype=torch.float32, device=dev)
+        terms = torch.empty(P, 5, **f32)
+        sums = torch.empty(P, 4, **f32)
+        hard = torch.empty(P, 4, dtype=torch.int32, device=dev)
+        loss = torch.empty(1, **f32)
+        num_valid = torch.empty(1, dtype=torch.int32, device=dev)
+        status = torch.empty(1, dtype=torch.int32, device=dev)
+        ws = torch.empty(lib.dcn_loss_workspace_bytes(P, lists.max_list_len), dtype=torch.uint8, device=dev)
+        records = None
+        if (ctx.needs_input_grad[0] or ctx.needs_input_grad[1]) and lists.capacity > 0:
+            records = torch.empty(lib.dcn_loss_saved_floats(lists.capacity, D), **f32)
+        rc = lib.dcn_contrastive_loss_mixed_forward(
+            _lib.ptr(desc_a), _lib.ptr(desc_b), P, HW, D, _lib.ptr(lists.idx_a), _lib.ptr(lists.idx_b), _lib.ptr(lists.offsets),
+            _lib.ptr(lists.types), table, lists.max_list_len, lists.max_pair_len, lists.capacity, _lib.ptr(terms),
+            _lib.ptr(sums), _lib.ptr(hard), _lib.ptr(loss), _lib.ptr(num_valid), _lib.ptr(status), _lib.ptr(ws),
+            _lib.ptr(records), _lib.stream_ptr())
+        _lib.check(rc, "dcn_contrastive_loss_mixed_forward")
+        ctx.save_for_backward(hard, num_valid)
+        ctx.records, ctx.lists, ctx.table, ctx.shape = records, lists, table, (P, HW, D)
+        ctx.mark_non_differentiable(terms, sums, hard, num_valid, status)
+        return loss.reshape(()), terms, sums, hard, num_valid, status
+
+    @staticmethod
+    def backward(ctx, grad_loss, *unused):
+        lib = _lib.get()
+        hard, num_valid = ctx.saved_tensors
+        lists, table = ctx.lists, ctx.table
+        P, HW, D = ctx.shape
+        g2 = torch.empty((2, P, HW, D), dtype=torch.float32, device=hard.device)
+        gl = grad_loss.reshape(1).to(torch.float32).contiguous()
+        exact_bytes = int(lib.dcn_loss_exact_workspace_bytes(P, HW, D))
+        exact = (EXACT_BACKWARD if EXACT_BACKWARD is not None else exact_bytes <= EXACT_BACKWARD_MAX_BYTES) and \
+            lists.max_pair_len < (1 << 22)            # (the bound, not the lengths: those stay on the device)
+        common = (P, HW, D, _lib.ptr(lists.idx_a), _lib.ptr(lists.idx_b), _lib.ptr(lists.offsets), _lib.ptr(lists.types), table,
+                  lists.max_list_len, lists.max_pair_len, lists.capacity, _lib.ptr(hard), _lib.ptr(num_valid), _lib.ptr(gl),
+                  _lib.ptr(ctx.records))
+        if exact:
+            ws = torch.empty(exact_bytes, dtype=torch.uint8, device=hard.device)
+            rc = lib.dcn_contrastive_loss_mixed_backward_saved_exact(*(common + (_lib.ptr(ws), _lib.ptr(g2[0]), _lib.ptr(g2[1]),
+                                                                                 _lib.stream_ptr())))
+            _lib.check(rc, "dcn_contrastive_loss_mixed_backward_saved_exact")
+        else:
+            rc = lib.dcn_contrastive_loss_mixed_backward_saved(*(common + (0, _lib.ptr(g2[0]), _lib.ptr(g2[1]),
+                                                                           _lib.stream_ptr())))
+            _lib.check(rc, "dcn_contrastive_loss_mixed_backward_saved")
+        return g2[0], g2[1], None, None
+
+
+def contrastive_loss_mixed(desc_a, desc_b, lists, cfgs):
+    """The fused forward (+ autograd) for a batch built on the device.  desc_*: [B, HW, D]; lists: ``DeviceLists``; cfgs: five
+    ``make_config`` results indexed by data type (or a ``config_table``): pair p composes with ``cfgs[types[p]]``, a pair of
+    type -1 is left out, ``loss = sum of the pairs kept / max(num_valid, 1)``.  Returns (loss 0-dim, terms [B,5], sums [B,4],
+    hard_neg int32 [B,4], num_valid int32 [1], status int32 [1], BAD_* bits) -- device tensors; no host synchronization."""
+    table = cfgs if isinstance(cfgs, ctypes.Array) else config_table(cfgs)
+    return _MixedLossFn.apply(desc_a, desc_b, lists, table)
+
+
 class _PerTermFn(torch.autograd.Function):
     """Differentiable per-pair vector (match: ||a-b||^2, non-match: l_j) -- pcl.py:171-213's first return value."""
 

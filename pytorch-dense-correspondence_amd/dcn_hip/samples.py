@@ -13,7 +13,7 @@ DIFFERENT_OBJECT): ``cross_scene_num_samples`` pixels of each mask, rotated, in 
 Masks are 0/1 (uint8, or anything ``.to(uint8)`` maps onto 0/1); other values are outside the contract (include/dcn_hip.h
 section 9).  Random numbers are drawn with the caller's generator into per-pair 64-bit seeds (the kernels hash them), or the
 reference's own ``torch.rand`` streams are replayed (``draws``).  Nothing here waits for the device, except
-``SampleBatch.pair_lists()`` (one read of the offsets).
+``SampleBatch.pair_lists()`` (one read of the offsets; ``SampleBatch.device_lists()`` has none).
 """
 import collections
 
@@ -26,6 +26,7 @@ from .pairgen import invert_rigid
 
 ONLY_OFF_MASK, MASK_INV = 1, 2
 BAD_INDEX, BAD_DRAWS, BAD_OFFSETS = 1, 2, 4
+CONCAT_MAX_GROUPS = 8
 SITES = ("cand", "masked", "background", "blind", "across_a", "across_b")
 CAM_FLOATS = 50
 SINGLE_OBJECT_WITHIN_SCENE, SINGLE_OBJECT_ACROSS_SCENE, DIFFERENT_OBJECT, MULTI_OBJECT, SYNTHETIC_MULTI_OBJECT = 0, 1, 2, 3, 4
@@ -36,12 +37,24 @@ SampleOptions = collections.namedtuple(
 
 
 class SampleBatch(collections.namedtuple(
-        "SampleBatch", "input_a input_b idx_a idx_b offsets empty type status seeds aug_params mask_a mask_b")):
+        "SampleBatch", "input_a input_b idx_a idx_b offsets empty type status seeds aug_params mask_a mask_b max_list_len "
+                       "max_pair_len", defaults=(None, None))):
     """input_a / input_b: float [B, 3, H, W] network inputs (None without RGB); idx_a / idx_b: int64 [capacity] device lists,
     pair p's list t (match, masked, background, blind) at ``offsets[4p+t]:offsets[4p+t+1]``, -1 after ``offsets[4B]``;
     offsets int64 [4B + 1]; empty bool [B]; type int32 [B] (data type, -1 for an empty pair); status int32 [1] (BAD_* bits);
     seeds int64 [B] (None when replayed); aug_params int32 [2B, 16]; mask_a / mask_b: the rotated masks, float 0/1
-    [B, H, W] (None without RGB)."""
+    [B, H, W] (None without RGB); max_list_len / max_pair_len: host ints, what no list / no pair's four lists can exceed by
+    the way the batch was built (None: unknown, the capacity ``idx_a.numel()`` is the bound)."""
+
+    def device_lists(self):
+        """A ``dcn_hip.loss.DeviceLists`` over ``idx_a`` / ``idx_b`` / ``offsets`` / ``type`` (no copy) for
+        ``loss_composer.get_loss_mixed``: the offsets stay on the device, the launches are shaped by the builders' bounds.
+        No host synchronization."""
+        from .loss import DeviceLists
+        cap = int(self.idx_a.numel())
+        return DeviceLists(self.idx_a, self.idx_b, self.offsets, self.type,
+                           cap if self.max_list_len is None else self.max_list_len,
+                           cap if self.max_pair_len is None else self.max_pair_len)
 
     def pair_lists(self):
         """A ``dcn_hip.loss.PairLists`` over ``idx_a`` / ``idx_b`` (no copy of the lists).  The loss API takes host offsets:
@@ -226,7 +239,8 @@ def build_within_scene_samples(depth_a, depth_b, mask_a, mask_b, pose_a, pose_b,
                                       P(typ), P(status), P(ws), _lib.stream_ptr())
     _lib.check(rc, "dcn_within_scene_samples")
     ia, ib, mka, mkb = _images(rgb_a, rgb_b, ma, mb, params, mean, std)
-    return SampleBatch(ia, ib, idx_a, idx_b, offsets, empty, typ, status, sd, params, mka, mkb)
+    return SampleBatch(ia, ib, idx_a, idx_b, offsets, empty, typ, status, sd, params, mka, mkb, max(A, A * k1, A * k2, h * w),
+                       cap // n)
 
 
 def build_across_scene_samples(mask_a, mask_b, rgb_a=None, rgb_b=None, *, num_samples, domain_randomize=False, flip=True,
@@ -253,7 +267,7 @@ def build_across_scene_samples(mask_a, mask_b, rgb_a=None, rgb_b=None, *, num_sa
                                       P(idx_b), cap, P(offsets), P(empty), P(typ), P(status), P(ws), _lib.stream_ptr())
     _lib.check(rc, "dcn_across_scene_samples")
     ia, ib, mka, mkb = _images(rgb_a, rgb_b, ma, mb, params, mean, std)
-    return SampleBatch(ia, ib, idx_a, idx_b, offsets, empty, typ, status, sd, params, mka, mkb)
+    return SampleBatch(ia, ib, idx_a, idx_b, offsets, empty, typ, status, sd, params, mka, mkb, ns, ns)
 
 
 def complete_samples(uv_a, uv_b, offsets, mask_a, mask_b, *, num_masked_non_matches_per_match,
@@ -295,4 +309,52 @@ def complete_samples(uv_a, uv_b, offsets, mask_a, mask_b, *, num_masked_non_matc
                                   P(idx_a), P(idx_b), cap, P(offsets_out), P(empty), P(typ), P(status), P(ws),
                                   _lib.stream_ptr())
     _lib.check(rc, "dcn_complete_samples")
-    return SampleBatch(None, None, idx_a, idx_b, offsets_out, empty, typ, status, sd, params, None, None)
+    return SampleBatch(None, None, idx_a, idx_b, offsets_out, empty, typ, status, sd, params, None, None,
+                       max(count, count * k1, count * k2, h * w), count * (1 + k1 + k2) + h * w)
+
+
+def _cat(parts):
+    return None if any(x is None for x in parts) else torch.cat(parts)
+
+
+def concat_sample_batches(batches):
+    """SampleBatches of one image size -- e.g. one per data type -- as ONE SampleBatch of B = sum of their sizes, pairs in
+    the order given: ``idx_a`` / ``idx_b`` compacted (pair p's four lists at ``offsets[4p+t]``, -1 after ``offsets[4B]``),
+    ``type`` / ``empty`` / ``seeds`` / ``aug_params`` / inputs / masks concatenated (None when a batch has none), ``status``
+    OR-ed (| BAD_OFFSETS for a batch whose offsets are not the builders' layout; its pairs then have empty lists), the bounds the
+    largest of the batches'.  Two launches and the concatenations; no host synchronization."""
+    batches = list(batches)
+    if not batches:
+        raise ValueError("concat_sample_batches needs at least one SampleBatch")
+    lib = _lib.get()
+    G = len(batches)
+    if G > CONCAT_MAX_GROUPS:
+        raise ValueError("at most %d batches are joined in one call, got %d" % (CONCAT_MAX_GROUPS, G))
+    dev = batches[0].idx_a.device
+    ns = [int(b.type.numel()) for b in batches]
+    caps = [int(b.idx_a.numel()) for b in batches]
+    if len({tuple(x.shape[-2:]) for b in batches for x in (b.input_a, b.mask_a) if x is not None}) > 1:
+        raise ValueError("concat_sample_batches: the batches' images differ in size")
+    src_a = [b.idx_a.contiguous() for b in batches]
+    src_b = [b.idx_b.contiguous() for b in batches]
+    src_o = [b.offsets.contiguous() for b in batches]
+    src_s = [b.status for b in batches]
+    _lib.require_device(*(src_a + src_b + src_o + src_s))
+    n, cap = sum(ns), sum(caps)
+    idx_a = torch.empty(max(cap, 1), dtype=torch.int64, device=dev)[:cap]
+    idx_b = torch.empty(max(cap, 1), dtype=torch.int64, device=dev)[:cap]
+    offsets = torch.empty(4 * n + 1, dtype=torch.int64, device=dev)
+    status = torch.empty(1, dtype=torch.int32, device=dev)
+    arr = lambda ts: (_lib.c_void_p * G)(*[None if t is None else t.data_ptr() for t in ts])
+    rc = lib.dcn_concat_samples(G, (_lib.c_int * G)(*ns), arr(src_a), arr(src_b), arr(src_o), (_lib.c_int64 * G)(*caps),
+                                arr(src_s), _lib.ptr(idx_a), _lib.ptr(idx_b), cap, _lib.ptr(offsets), _lib.ptr(status),
+                                _lib.stream_ptr())
+    _lib.check(rc, "dcn_concat_samples")
+    params = None
+    if all(b.aug_params is not None for b in batches):      # [2B, 16]: a's records first, then b's
+        params = torch.cat([b.aug_params[:k] for b, k in zip(batches, ns)] + [b.aug_params[k:] for b, k in zip(batches, ns)])
+    bound = lambda k: None if any(getattr(b, k) is None for b in batches) else max(getattr(b, k) for b in batches)
+    return SampleBatch(_cat([b.input_a for b in batches]), _cat([b.input_b for b in batches]), idx_a, idx_b, offsets,
+                       torch.cat([b.empty for b in batches]), torch.cat([b.type for b in batches]), status,
+                       _cat([b.seeds for b in batches]), params, _cat([b.mask_a for b in batches]),
+                       _cat([b.mask_b for b in batches]), bound("max_list_len"), bound("max_pair_len"))

@@ -80,6 +80,35 @@ def get_loss_batched(pixelwise_contrastive_loss, match_type, image_a_pred, image
     return loss, terms, hard
 
 
+STATUS_MESSAGES = ((_k.BAD_INDEX, IndexError, "pixel index outside [0, H*W) in a pair list"),
+                   (_k.BAD_TYPE, ValueError, "data type outside {-1, 0 .. 4}"),
+                   (_k.BAD_BOUNDS, ValueError, "a list or pair longer than the bounds of its DeviceLists, or offsets beyond "
+                                               "the lists' capacity"),
+                   (_k.BAD_PIXEL_LAYOUT, RuntimeError, "pixel-distance weighting needs a whole number of non-matches per "
+                                                       "match (pixelwise_contrastive_loss.py:321-325)"))
+
+
+def get_loss_mixed(pixelwise_contrastive_loss, image_a_pred, image_b_pred, lists):
+    """The loss of a batch built on the device, as it is.  image_*_pred: [B, W*H, D]; lists: ``dcn_hip.loss.DeviceLists``
+    (``SampleBatch.device_lists()``): device offsets and one data type per pair.  Every pair composes as ``get_loss`` does for
+    its own type (SYNTHETIC_MULTI_OBJECT as within-scene); a pair of type -1 -- the reference's ``return_empty_data`` sample,
+    which its training loop skips (training.py:304-306) -- is left out of the mean: ``loss = sum of the pairs kept /
+    max(num_valid, 1)``, its rows of ``terms`` / ``hard_negatives`` and its gradient are zero.
+    Returns (loss, terms [B,5], hard_negatives int32 [B,4], num_valid int32 [1]) -- all device tensors, nothing read back."""
+    pcl = pixelwise_contrastive_loss
+    table = _k.config_table([_kernel_config(pcl, code) for code in range(_k.NUM_TYPES)])
+    loss, terms, sums, hard, num_valid, status = _k.contrastive_loss_mixed(image_a_pred, image_b_pred, lists, table)
+    # status (device int32): dcn_hip.loss.BAD_* bits -- what _check_pixel_layout and PairLists.from_lists raise for on the host
+    # is flagged on the device here.  Kept on the loss object (no sync on the hot path); with `debug` on it is read and raised.
+    pcl.last_status = status
+    if getattr(pcl, "debug", False):
+        bits = int(status.item())
+        for bit, exc, what in STATUS_MESSAGES:
+            if bits & bit:
+                raise exc("%s (pixelwise_contrastive_loss.debug check, status %d)" % (what, bits))
+    return loss, terms, hard, num_valid
+
+
 def get_loss(pixelwise_contrastive_loss, match_type, image_a_pred, image_b_pred, matches_a, matches_b,
              masked_non_matches_a, masked_non_matches_b, background_non_matches_a, background_non_matches_b,
              blind_non_matches_a, blind_non_matches_b):
