@@ -855,6 +855,79 @@ int dcn_gather_frames(int n, int frames_per_pair, const struct dcn_frame_store* 
                       const uint8_t* empty, uint8_t* rgb, uint16_t* depth, uint8_t* mask, float* cams, int32_t* status,
                       void* stream);
 
+/* =====================================================================================================
+ * 11. Evaluation on frame-store image pairs -- replaces, for device-resident frames and descriptor images, what
+ *     DenseCorrespondenceEvaluation.evaluate_network (dense_correspondence/evaluation/evaluation.py:475-527) runs per image
+ *     pair: the match search and subsample of single_same_scene_image_pair_quantitative_analysis (:908-921) and
+ *     compute_descriptor_match_statistics (:1045-1175) for every chosen match, for ALL pairs in one call each.
+ *
+ * 11a. Matches: per pair batch_find_pixel_correspondences(depth_a, pose_a, depth_b, pose_b, img_a_mask=mask_a): `attempts`
+ *     candidates from mask a's pixels and the reprojection test, exactly the first stages of dcn_within_scene_samples
+ *     (section 9: same device functions, cams, seeds / rand / rand_offsets replay of site DCN_SAMPLE_SITE_CAND; the other
+ *     sites' offsets are not read), kept as (u_a, v_a) int64 and the FLOAT projection (u_b, v_b).  Then the subsample
+ *     random.sample(range(total), min(num_matches, total)) (:919-921) as a device stage: pair p contributes
+ *     k_p = min(num_matches, total_p) rows, row j is survivor match_order[p][j] (replay: int32 [n][num_matches], -1 padded,
+ *     the reference's match_list; a position outside [0, total_p) reads 0 and raises DCN_SAMPLE_BAD_DRAWS), or, with
+ *     match_order == NULL, the survivor of rank j when the total_p survivors are ordered by a hash of (order_seeds[p],
+ *     survivor) -- a uniform random order, its first k_p entries.
+ *     Outputs: rows [offsets[p], offsets[p+1]) of u_a, v_a (int64), u_b, v_b (float), each [n * min(num_matches, attempts)],
+ *     -1 / 0 from offsets[n] on; offsets int64 [n + 1]; totals int32 [n]; status int32 [1] (DCN_SAMPLE_* bits, written).
+ *     A pair with no survivor (or an empty mask a) has no rows.  1 <= n <= 1024, 1 <= attempts <= 4096.
+ *
+ * 11b. Statistics: P pairs of [h][w] images; res_a, res_b float [P][hw][d] descriptor images; mask_b uint8 [P][hw] (non-zero:
+ *     on the object); depth_a, depth_b uint16 [P][hw] millimetres; cams [P][DCN_SAMPLE_CAM_FLOATS] (section 9's rows);
+ *     the query rows of pair p at [offsets[p], offsets[p+1]) of u_a, v_a (int64), u_b, v_b (float, as 11a returns them);
+ *     offsets int64 [P + 1] on the device.  max_rows: the rows' capacity (every output's row dimension); max_pair_rows: a
+ *     bound on one pair's rows (a longer list is cut there and raises DCN_EVAL_BAD_OFFSETS).  offsets must increase from >= 0
+ *     to <= max_rows over all pairs: one violation anywhere raises DCN_EVAL_BAD_OFFSETS and every pair is then empty.
+ *     Ground-truth pixel: clip_pixel_to_image_size_and_round (:604-607), min(int(round(x)), size - 1) with Python 2's round
+ *     (half away from zero), and not below 0.
+ *     Stage A, one launch over (pixel tile, pair): dcn_match_statistics' scheme (section 4) with the query descriptors
+ *     res_a[p][v_a * w + u_a] gathered by the kernel, and the count of mask b's non-zero pixels.  Stage B, one work-item per
+ *     row, writes
+ *       columns double [DCN_EVAL_COLUMNS][max_rows] (DCN_EVAL_COL_*: the DCNEvaluationPandaTemplate columns, :37-63)
+ *       is_valid uint8 [2][max_rows] (is_valid, is_valid_masked); pred_uv int32 [4][max_rows] (u, v of the best match over the
+ *       image; u, v over the mask); closer int32 [2][max_rows] (pixels closer than the ground truth: image, masked);
+ *       row_pair int32 [max_rows]; mask_pixels int32 [P]; status int32 [1] (DCN_EVAL_* bits, written).
+ *     Rows from offsets[P] on: NaN columns, zero flags / counts, -1 in pred_uv and row_pair.
+ *     Depth / 3D columns (:1102-1135, :1148-1164) in float64: depth / 1000.0, valid when 0 < d < 10; position = pose *
+ *     (z * K^-1 * (u, v, 1)) with K^-1 the float64 inverse of the row's fp32 K, pose a the row's fp32 pose a, and pose b the
+ *     float64 rigid inverse (R^T, -(R^T t)) of the row's fp32 pose b^-1; norm_diff_ground_truth_3d is NaN unless the ground
+ *     truth's depth in b is valid, norm_diff_pred_3d[_masked] NaN unless that and the predicted pixel's depth are valid.
+ *     fraction_..._masked of a pair whose mask b is empty is NaN (the reference divides by zero there).  The false positives'
+ *     pixel distances are summed as integers of 2^-20 pixel, so the averages do not depend on the order of the atomics.
+ *     No host synchronisation.  1 <= P <= 65535, 1 <= d <= 64, h * w < 2^31.
+ * ===================================================================================================== */
+#define DCN_EVAL_COLUMNS 13
+#define DCN_EVAL_COL_NORM_DIFF_DESCRIPTOR_GROUND_TRUTH 0
+#define DCN_EVAL_COL_NORM_DIFF_DESCRIPTOR 1
+#define DCN_EVAL_COL_NORM_DIFF_DESCRIPTOR_MASKED 2
+#define DCN_EVAL_COL_NORM_DIFF_GROUND_TRUTH_3D 3
+#define DCN_EVAL_COL_NORM_DIFF_PRED_3D 4
+#define DCN_EVAL_COL_NORM_DIFF_PRED_3D_MASKED 5
+#define DCN_EVAL_COL_PIXEL_MATCH_ERROR_L2 6
+#define DCN_EVAL_COL_PIXEL_MATCH_ERROR_L2_MASKED 7
+#define DCN_EVAL_COL_PIXEL_MATCH_ERROR_L1 8
+#define DCN_EVAL_COL_FRACTION_CLOSER 9
+#define DCN_EVAL_COL_FRACTION_CLOSER_MASKED 10
+#define DCN_EVAL_COL_AVERAGE_L2_FALSE_POSITIVES 11
+#define DCN_EVAL_COL_AVERAGE_L2_FALSE_POSITIVES_MASKED 12
+#define DCN_EVAL_BAD_INDEX 1        /* status: a query pixel outside the image, or a ground truth that is NaN / negative (read as 0) */
+#define DCN_EVAL_BAD_OFFSETS 2      /* status: offsets not increasing within [0, max_rows] (every pair empty), or a pair above max_pair_rows */
+#define DCN_EVAL_BAD_DRAWS 4        /* dcn_hip.evaluate only: the match search's DCN_SAMPLE_BAD_DRAWS (a bad replay stream or match_order) */
+#define DCN_EVAL_BAD_FRAME 8        /* dcn_hip.evaluate only: the gather's DCN_FRAME_BAD_INDEX */
+size_t dcn_eval_matches_workspace(int n, int h, int w, int64_t attempts);
+int dcn_eval_matches(int n, int h, int w, const uint16_t* depth_a, const uint16_t* depth_b, const uint8_t* mask_a,
+                     const float* cams, int64_t attempts, const int64_t* seeds, const float* rand, const int64_t* rand_offsets,
+                     int num_matches, const int32_t* match_order, const int64_t* order_seeds, int64_t* u_a, int64_t* v_a,
+                     float* u_b, float* v_b, int64_t* offsets, int32_t* totals, int32_t* status, void* workspace, void* stream);
+size_t dcn_match_statistics_pairs_workspace(int64_t max_rows);
+int dcn_match_statistics_pairs(int p, int h, int w, int d, const float* res_a, const float* res_b, const uint8_t* mask_b,
+                               const uint16_t* depth_a, const uint16_t* depth_b, const float* cams, const int64_t* u_a,
+                               const int64_t* v_a, const float* u_b, const float* v_b, const int64_t* offsets, int64_t max_rows,
+                               int max_pair_rows, double* columns, uint8_t* is_valid, int32_t* pred_uv, int32_t* closer,
+                               int32_t* row_pair, int32_t* mask_pixels, int32_t* status, void* workspace, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -15,6 +15,8 @@
 //   write_kernel        ONE pass over the whole output capacity: each work-item owns 4 consecutive entries, finds its
 //                       (pair, list, entry) by a binary search over the offsets held in LDS, writes idx_a / idx_b int64
 //                       (16-byte stores) and -1 past offsets[4n].
+//   eval_offsets_kernel / eval_select_kernel   matches only (section 11a, the evaluation): the kept candidates with their
+//                       float projections, subsampled like random.sample, in match_list order.
 //
 // Random numbers: uniform on torch.rand's 24-bit grid from a counter-based hash of (pair seed, site, index), or replayed from
 // the caller's streams (include/dcn_hip.h section 9).
@@ -582,6 +584,100 @@ inline OutArgs out_of(const Workspace& ws, int n, int h, int w, const int32_t* p
     return o;
 }
 
+// ---- matches only, for the evaluation (include/dcn_hip.h section 11a): the kept candidates with their FLOAT projections, then
+// the subsample random.sample(range(total), min(num_matches, total)) of evaluation.py:919-921.
+struct EvalArgs {
+    const int32_t* sel;            // [n][ls]-strided lists of SRC_FLAGS: kept candidate indices
+    const int64_t* count;          // [n] kept candidates
+    const int32_t* pix;
+    const float* u2;
+    const float* v2;
+    const int32_t* order;          // [n][num_matches] replay positions, -1 padded, or null
+    const int64_t* seeds;          // [n] (order == null)
+    int64_t* ua;                   // [n * rpp]
+    int64_t* va;
+    float* ub;
+    float* vb;
+    int64_t* offsets;              // [n + 1]
+    int32_t* totals;               // [n]
+    int32_t* status;
+    int64_t attempts, ls;
+    int n, w, num_matches, rpp;    // rpp = min(num_matches, attempts): rows per pair at most
+};
+
+// one workgroup: offsets[p + 1] = offsets[p] + min(num_matches, total_p)
+__global__ void __launch_bounds__(1024) eval_offsets_kernel(EvalArgs a) {
+    __shared__ int32_t k_s[kMaxPairs];
+    for (int p = threadIdx.x; p < a.n; p += 1024) {
+        const int64_t t = a.count[p];
+        a.totals[p] = (int32_t)t;
+        k_s[p] = (int32_t)(t < a.num_matches ? t : a.num_matches);
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        int64_t o = 0;
+        a.offsets[0] = 0;
+        for (int p = 0; p < a.n; ++p) {
+            o += k_s[p];
+            a.offsets[p + 1] = o;
+        }
+    }
+}
+
+__device__ __forceinline__ uint32_t order_key(uint64_t s, uint32_t i) {
+    const uint32_t k0 = mix32((uint32_t)s ^ 0x2545F491U);
+    return mix32(mix32(i ^ k0) ^ (mix32((uint32_t)(s >> 32) ^ k0) + 0x9E3779B9U));
+}
+
+// grid (ceil(attempts / 256), n): work-item e of pair p.  Replay: e < k is output row e, survivor order[p][e].  Seeded: e <
+// total is survivor e, whose rank among the total hashed keys (ties by index) is its row when below k.  Every work-item with
+// e < rpp also owns entry p * rpp + e of the outputs' tail (-1 / 0 from offsets[n] on).
+__global__ void __launch_bounds__(kThreads) eval_select_kernel(EvalArgs a) {
+    const int p = blockIdx.y;
+    const int64_t e = (int64_t)blockIdx.x * kThreads + threadIdx.x;
+    const int64_t total = a.count[p], k = total < a.num_matches ? total : a.num_matches;
+    const int64_t base = a.offsets[p], end = a.offsets[a.n];
+    if (e < a.rpp) {
+        const int64_t g = (int64_t)p * a.rpp + e;
+        if (g >= end) {
+            a.ua[g] = -1;
+            a.va[g] = -1;
+            a.ub[g] = 0.f;
+            a.vb[g] = 0.f;
+        }
+    }
+    int64_t row = -1, i = 0;
+    if (a.order) {
+        if (e < k) {
+            row = e;
+            i = a.order[(size_t)p * a.num_matches + e];
+            if (i < 0 || i >= total) {
+                atomicOr(a.status, DCN_SAMPLE_BAD_DRAWS);
+                i = 0;
+            }
+        }
+    } else if (e < total) {
+        const uint64_t s = (uint64_t)a.seeds[p];
+        const uint32_t mine = order_key(s, (uint32_t)e);
+        int64_t rank = 0;
+        for (int64_t j = 0; j < total; ++j) {
+            const uint32_t o = order_key(s, (uint32_t)j);
+            rank += (o < mine || (o == mine && j < e)) ? 1 : 0;
+        }
+        if (rank < k) {
+            row = rank;
+            i = e;
+        }
+    }
+    if (row < 0) return;
+    const int64_t c = (int64_t)p * a.attempts + a.sel[(size_t)p * a.ls + i];
+    const int64_t px = a.pix[c];
+    a.ua[base + row] = px % a.w;
+    a.va[base + row] = px / a.w;
+    a.ub[base + row] = a.u2[c];
+    a.vb[base + row] = a.v2[c];
+}
+
 // stages 4 - 6 after the matches (ma / mb / mcount / matched are in the workspace)
 inline int finish_within(const Workspace& ws, Common c, OutArgs o, hipStream_t st) {
     compact(c, (1u << SRC_BLIND) | (1u << SRC_MB) | (o.inv ? (1u << SRC_MBINV) : 0u), st);
@@ -594,6 +690,78 @@ inline int finish_within(const Workspace& ws, Common c, OutArgs o, hipStream_t s
 extern "C" size_t dcn_sample_workspace(int n, int h, int w, int64_t attempts, int64_t match_slots) {
     if (n < 1 || h < 1 || w < 1 || attempts < 0 || match_slots < 0) return 0;
     return carve(nullptr, nullptr, n, (int64_t)h * w, attempts, match_slots);
+}
+
+extern "C" size_t dcn_eval_matches_workspace(int n, int h, int w, int64_t attempts) {
+    if (n < 1 || h < 1 || w < 1 || attempts < 1) return 0;
+    return carve(nullptr, nullptr, n, (int64_t)h * w, attempts, 1);
+}
+
+extern "C" int dcn_eval_matches(int n, int h, int w, const uint16_t* depth_a, const uint16_t* depth_b, const uint8_t* mask_a,
+                                const float* cams, int64_t attempts, const int64_t* seeds, const float* rand,
+                                const int64_t* rand_offsets, int num_matches, const int32_t* match_order,
+                                const int64_t* order_seeds, int64_t* u_a, int64_t* v_a, float* u_b, float* v_b, int64_t* offsets,
+                                int32_t* totals, int32_t* status, void* workspace, void* stream) {
+    const int64_t hw = (int64_t)h * w;
+    if (!shape_ok(n, h, w) || !depth_a || !depth_b || !mask_a || !cams || attempts < 1 || attempts > 4096 ||
+        (!seeds && (!rand || !rand_offsets)) || num_matches < 1 || (!match_order && !order_seeds) || !u_a || !v_a || !u_b ||
+        !v_b || !offsets || !totals || !status || !workspace)
+        return DCN_E_INVALID;
+    hipStream_t st = (hipStream_t)stream;
+    Workspace ws;
+    carve(&ws, (char*)workspace, n, hw, attempts, 1);
+    int rc = dcn::fill_bytes_async(status, 0, 4, st);
+    if (rc != DCN_OK) return rc;
+    Common c = common_of(ws, n, h, w, attempts, mask_a, mask_a, nullptr);
+    compact(c, 1u << SRC_A0, st);
+    const int64_t ls = hw > attempts ? hw : attempts;
+    CandArgs ca;
+    ca.depth_a = depth_a;
+    ca.depth_b = depth_b;
+    ca.cams = cams;
+    ca.d = draws_of(n, seeds, rand, rand_offsets);
+    ca.flags = ws.flags;
+    ca.u2 = ws.u2;
+    ca.v2 = ws.v2;
+    ca.pix = ws.pix;
+    ca.list_a = ws.lists + (size_t)SRC_A0 * n * ls;
+    ca.count_a = ws.counts + (size_t)SRC_A0 * n;
+    ca.status = status;
+    ca.attempts = attempts;
+    ca.hw = hw;
+    ca.ls = ls;
+    ca.n = n;
+    ca.h = h;
+    ca.w = w;
+    ca.from_mask = 1;
+    hipLaunchKernelGGL(candidate_kernel, dim3((unsigned)dcn::ceil_div64(attempts, kThreads), (unsigned)n), dim3(kThreads), 0, st,
+                       ca);
+    compact(c, 1u << SRC_FLAGS, st);
+    EvalArgs e;
+    e.sel = ws.lists + (size_t)SRC_FLAGS * n * ls;
+    e.count = ws.counts + (size_t)SRC_FLAGS * n;
+    e.pix = ws.pix;
+    e.u2 = ws.u2;
+    e.v2 = ws.v2;
+    e.order = match_order;
+    e.seeds = order_seeds;
+    e.ua = u_a;
+    e.va = v_a;
+    e.ub = u_b;
+    e.vb = v_b;
+    e.offsets = offsets;
+    e.totals = totals;
+    e.status = status;
+    e.attempts = attempts;
+    e.ls = ls;
+    e.n = n;
+    e.w = w;
+    e.num_matches = num_matches;
+    e.rpp = (int)(num_matches < attempts ? num_matches : attempts);
+    hipLaunchKernelGGL(eval_offsets_kernel, dim3(1), dim3(1024), 0, st, e);
+    hipLaunchKernelGGL(eval_select_kernel, dim3((unsigned)dcn::ceil_div64(attempts, kThreads), (unsigned)n), dim3(kThreads), 0, st,
+                       e);
+    return dcn::check_launch();
 }
 
 extern "C" int dcn_within_scene_samples(int n, int h, int w, const uint16_t* depth_a, const uint16_t* depth_b,

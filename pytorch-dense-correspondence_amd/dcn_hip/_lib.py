@@ -210,6 +210,12 @@ SYMBOLS = {
     "dcn_select_frames": (c_int, [c_int, c_int, ctypes.POINTER(FrameStoreDesc), c_int, ctypes.c_double, ctypes.c_double]
                           + [c_void_p] * 8),
     "dcn_gather_frames": (c_int, [c_int, c_int, ctypes.POINTER(FrameStoreDesc)] + [c_void_p] * 8),
+    "dcn_eval_matches_workspace": (c_size_t, [c_int, c_int, c_int, c_int64]),
+    "dcn_eval_matches": (c_int, [c_int, c_int, c_int] + [c_void_p] * 4 + [c_int64] + [c_void_p] * 3 + [c_int]
+                         + [c_void_p] * 11),
+    "dcn_match_statistics_pairs_workspace": (c_size_t, [c_int64]),
+    "dcn_match_statistics_pairs": (c_int, [c_int, c_int, c_int, c_int] + [c_void_p] * 11 + [c_int64, c_int]
+                                   + [c_void_p] * 9),
 }
 
 ERRORS = {-1: "DCN_E_INVALID (bad argument)", -2: "DCN_E_LAUNCH (kernel launch failed)",

@@ -1,0 +1,303 @@
+"""Host side of the evaluation kernels (csrc/evaluate_kernels.hip, the matches-only entry of csrc/sample_kernels.hip): the
+reference's quantitative evaluation, ``DenseCorrespondenceEvaluation.evaluate_network``
+(dense_correspondence/evaluation/evaluation.py:475-527) and what it calls per image pair
+(single_same_scene_image_pair_quantitative_analysis :862-958, compute_descriptor_match_statistics :1007-1178), on the frames
+of a ``frames.FrameStore``.
+
+``choose_pairs`` draws the image pairs on the host (a few integers per pair).  ``evaluate_frame_pairs`` then gathers the
+frames, normalizes them, runs the network in eval mode, finds and subsamples the ground-truth matches and computes every
+column of the reference's table for all pairs, without reading anything back; ``evaluate_network`` composes the two and
+copies the table to the host once.
+"""
+import collections
+import ctypes
+
+import numpy as np
+import torch
+
+from . import _lib
+from . import augment as _aug
+from .samples import CAM_FLOATS, _depth, _mask, _random, draw_seeds
+
+COLUMNS = ("norm_diff_descriptor_ground_truth", "norm_diff_descriptor", "norm_diff_descriptor_masked",
+           "norm_diff_ground_truth_3d", "norm_diff_pred_3d", "norm_diff_pred_3d_masked", "pixel_match_error_l2",
+           "pixel_match_error_l2_masked", "pixel_match_error_l1", "fraction_pixels_closer_than_ground_truth",
+           "fraction_pixels_closer_than_ground_truth_masked", "average_l2_distance_for_false_positives",
+           "average_l2_distance_for_false_positives_masked")
+BAD_INDEX, BAD_OFFSETS, BAD_DRAWS, BAD_FRAME = 1, 2, 4, 8
+NUM_ATTEMPTS = 20          # batch_find_pixel_correspondences' default num_attempts, which the evaluation uses (:908)
+
+
+class EvalTable(collections.namedtuple(
+        "EvalTable", "columns is_valid pred_uv closer row_pair offsets mask_pixels status u_a v_a u_b v_b")):
+    """Device tensors, R = the row capacity; the rows in use are [0, offsets[-1]), pair p's at offsets[p]:offsets[p+1].
+    columns float64 [13, R] in the order of COLUMNS (NaN past the last row); is_valid uint8 [2, R] (is_valid,
+    is_valid_masked); pred_uv int32 [4, R] (u, v of the best match over the image, u, v over the mask; -1 past the last row);
+    closer int32 [2, R] (pixels closer than the ground truth: image, masked); row_pair int32 [R] (the row's pair, -1 past the
+    last row); offsets int64 [P + 1]; mask_pixels int32 [P]; status int32 [1] (BAD_INDEX | BAD_OFFSETS from the statistics; evaluate_frame_pairs adds
+    BAD_DRAWS for a replay stream or ``match_order`` the match search rejected and BAD_FRAME for a frame the gather rejected); u_a, v_a int64 [R]
+    and u_b, v_b float32 [R]: the query rows."""
+
+    def column(self, name):
+        return self.columns[COLUMNS.index(name)]
+
+
+def _rows(t, dtype, what, count=None):
+    if t.dtype != dtype or t.dim() != 1 or (count is not None and int(t.numel()) != count):
+        raise ValueError("%s must be a 1-D %s tensor%s, got %s %s" % (what, dtype, "" if count is None else " of %d" % count,
+                                                                     t.dtype, tuple(t.shape)))
+    return t.contiguous()
+
+
+def match_statistics_pairs(res_a, res_b, mask_b, depth_a, depth_b, cams, u_a, v_a, u_b, v_b, offsets, max_pair_rows=None):
+    """Every column of the reference's evaluation table for the query rows of P image pairs, in two launches.
+
+    res_a, res_b: float32 [P, H, W, D] descriptor images; mask_b: [P, H, W] (non-zero = on the object); depth_a, depth_b: 16-bit
+    [P, H, W] millimetres; cams: float32 [P, 50] camera rows (K, K^-1, pose a, pose b^-1; frames.FrameBatch.cams[0]); u_a, v_a:
+    int64 [R] query pixels in image a; u_b, v_b: float32 [R] ground truth in image b as the correspondence search returns it
+    (rounded and clipped like the reference); offsets: int64 [P + 1] device tensor, pair p's rows at offsets[p]:offsets[p+1]
+    (rows from offsets[P] on are ignored).  max_pair_rows: a bound on one pair's rows (default R).
+    -> EvalTable.  No host synchronization."""
+    lib = _lib.get()
+    if res_a.dim() != 4 or res_a.shape != res_b.shape:
+        raise ValueError("res_a and res_b must be [P, H, W, D] of one shape, got %s and %s" % (tuple(res_a.shape),
+                                                                                          tuple(res_b.shape)))
+    P, h, w, d = (int(s) for s in res_a.shape)
+    if d < 1 or d > 64:
+        raise ValueError("descriptor dimension must be 1 .. 64, got %d" % d)
+    ra, rb = res_a.contiguous().float(), res_b.contiguous().float()
+    mb = _mask(mask_b, P, h, w, "mask_b")
+    da, db = _depth(depth_a, P, h, w, "depth_a"), _depth(depth_b, P, h, w, "depth_b")
+    if tuple(cams.shape) != (P, CAM_FLOATS) or cams.dtype != torch.float32:
+        raise ValueError("cams must be float32 [%d, %d], got %s %s" % (P, CAM_FLOATS, cams.dtype, tuple(cams.shape)))
+    cams = cams.contiguous()
+    ua = _rows(u_a, torch.int64, "u_a")
+    R = int(ua.numel())
+    va, ub, vb = _rows(v_a, torch.int64, "v_a", R), _rows(u_b, torch.float32, "u_b", R), _rows(v_b, torch.float32, "v_b", R)
+    if not torch.is_tensor(offsets) or offsets.dtype != torch.int64 or int(offsets.numel()) != P + 1:
+        raise ValueError("offsets must be an int64 tensor of P + 1 = %d entries" % (P + 1))
+    off = offsets.contiguous().view(-1)
+    _lib.require_device(ra, rb, mb, da, db, cams, ua, va, ub, vb, off)
+    dev = ra.device
+    cap = max(R, 1)
+    if R == 0:                                             # (no rows at all: the kernels still want valid pointers)
+        ua = va = torch.zeros(1, dtype=torch.int64, device=dev)
+        ub = vb = torch.zeros(1, dtype=torch.float32, device=dev)
+    mpr = cap if max_pair_rows is None else max(1, min(int(max_pair_rows), cap))
+    cols = torch.empty((len(COLUMNS), cap), dtype=torch.float64, device=dev)
+    valid = torch.empty((2, cap), dtype=torch.uint8, device=dev)
+    pred = torch.empty((4, cap), dtype=torch.int32, device=dev)
+    closer = torch.empty((2, cap), dtype=torch.int32, device=dev)
+    row_pair = torch.empty(cap, dtype=torch.int32, device=dev)
+    mask_pixels = torch.empty(P, dtype=torch.int32, device=dev)
+    status = torch.empty(1, dtype=torch.int32, device=dev)
+    ws = torch.empty(int(lib.dcn_match_statistics_pairs_workspace(cap)), dtype=torch.uint8, device=dev)
+    p = _lib.ptr
+    rc = lib.dcn_match_statistics_pairs(P, h, w, d, p(ra), p(rb), p(mb), p(da), p(db), p(cams), p(ua), p(va), p(ub), p(vb),
+                                        p(off), cap, mpr, p(cols), p(valid), p(pred), p(closer), p(row_pair), p(mask_pixels),
+                                        p(status), p(ws), _lib.stream_ptr())
+    _lib.check(rc, "dcn_match_statistics_pairs")
+    return EvalTable(cols[:, :R], valid[:, :R], pred[:, :R], closer[:, :R], row_pair[:R], off, mask_pixels, status,
+                     u_a, v_a, u_b, v_b)
+
+
+EvalMatches = collections.namedtuple("EvalMatches", "u_a v_a u_b v_b offsets totals status order_seeds")
+
+
+def find_eval_matches(depth_a, depth_b, mask_a, cams, num_matches=100, *, num_attempts=NUM_ATTEMPTS, generator=None,
+                      draws=None, seeds=None, match_order=None, order_seeds=None):
+    """The ground-truth matches the evaluation uses, per pair: ``batch_find_pixel_correspondences(depth_a, pose_a, depth_b,
+    pose_b, img_a_mask=mask_a)`` with ``num_attempts`` candidates from mask a's pixels (the search of
+    samples.build_within_scene_samples, without non-matches or rotation), then ``random.sample(range(total), min(num_matches,
+    total))`` (evaluation.py:919-921) on the device.
+
+    depth_a, depth_b: 16-bit [P, H, W]; mask_a: [P, H, W]; cams: float32 [P, 50].  ``draws``: {"cand": per-pair torch.rand
+    streams} to replay (samples.pack_draws), otherwise per-pair ``seeds`` (drawn with ``generator`` when None).
+    ``match_order``: int [P, num_matches], -1 padded, the reference's ``match_list`` per pair to replay; otherwise the order
+    comes from ``order_seeds`` (int64 [P], drawn with ``generator`` when None).
+    -> EvalMatches: u_a, v_a int64 and u_b, v_b float32 [P * min(num_matches, num_attempts)], pair p's rows at
+    offsets[p]:offsets[p+1] in ``match_list`` order (a pair without matches has none; -1 / 0 after offsets[P]); totals int32
+    [P] (matches found before the subsample); status int32 [1] (samples.BAD_DRAWS).  No host synchronization."""
+    lib = _lib.get()
+    n, h, w = int(mask_a.shape[0]), int(mask_a.shape[1]), int(mask_a.shape[2])
+    dev = mask_a.device
+    da, db = _depth(depth_a, n, h, w, "depth_a"), _depth(depth_b, n, h, w, "depth_b")
+    ma = _mask(mask_a, n, h, w, "mask_a")
+    A, M = int(num_attempts), int(num_matches)
+    if A < 1 or A > 4096 or M < 1 or n > 1024:
+        raise ValueError("num_attempts must be 1 .. 4096, num_matches >= 1 and at most 1024 pairs per call")
+    if tuple(cams.shape) != (n, CAM_FLOATS) or cams.dtype != torch.float32:
+        raise ValueError("cams must be float32 [%d, %d], got %s %s" % (n, CAM_FLOATS, cams.dtype, tuple(cams.shape)))
+    cams = cams.contiguous()
+    sd, rand, roff = _random(n, dev, generator, draws, seeds)
+    order = osd = None
+    if match_order is not None:
+        order = torch.as_tensor(np.asarray(match_order.cpu() if torch.is_tensor(match_order) else match_order,
+                                           np.int64).astype(np.int32))
+        if tuple(order.shape) != (n, M):
+            raise ValueError("match_order must be [%d, %d] (-1 padded), got %s" % (n, M, tuple(order.shape)))
+        order = order.to(dev).contiguous()
+    elif order_seeds is None:
+        osd = draw_seeds(n, dev, generator)
+    else:
+        osd = torch.as_tensor(order_seeds).to(device=dev, dtype=torch.int64).contiguous().view(-1)
+        if osd.numel() != n:
+            raise ValueError("order_seeds must hold one int64 per pair (%d)" % n)
+    _lib.require_device(da, db, ma, cams, sd, rand, roff, order, osd)
+    cap = n * min(M, A)
+    ua, va = torch.empty(cap, dtype=torch.int64, device=dev), torch.empty(cap, dtype=torch.int64, device=dev)
+    ub, vb = torch.empty(cap, dtype=torch.float32, device=dev), torch.empty(cap, dtype=torch.float32, device=dev)
+    offsets = torch.empty(n + 1, dtype=torch.int64, device=dev)
+    totals = torch.empty(n, dtype=torch.int32, device=dev)
+    status = torch.empty(1, dtype=torch.int32, device=dev)
+    ws = torch.empty(int(lib.dcn_eval_matches_workspace(n, h, w, A)), dtype=torch.uint8, device=dev)
+    p = _lib.ptr
+    rc = lib.dcn_eval_matches(n, h, w, p(da), p(db), p(ma), p(cams), A, p(sd), p(rand), p(roff), M, p(order), p(osd), p(ua),
+                              p(va), p(ub), p(vb), p(offsets), p(totals), p(status), p(ws), _lib.stream_ptr())
+    _lib.check(rc, "dcn_eval_matches")
+    return EvalMatches(ua, va, ub, vb, offsets, totals, status, osd)
+
+
+def _below(rng, n):
+    return int(rng.integers(n)) if hasattr(rng, "integers") else int(rng.randint(n))
+
+
+def choose_pairs(store, num_image_pairs, host_rng=None, threshold=0.05, max_num_attempts=100):
+    """``num_image_pairs`` times the reference's per-pair rule, on the host: a scene by ``get_random_scene_name``
+    (spartan_dataset_masked.py:521-541: one lot per multi-object scene and per object; then uniform over the multi-object
+    scenes, or a uniform object and a uniform scene of it), image a uniform over the scene's frames, image b the first of up
+    to ``max_num_attempts`` uniform frames whose translation differs from a's by more than ``threshold`` (float64 norm,
+    ``get_image_pair_with_poses_diff_above_threshold``, evaluation.py:175-203); a pair for which none does is skipped, as
+    ``evaluate_network`` skips ``None``.  Reads ``store.translations_host``; ``host_rng``: a numpy RandomState / Generator
+    (default ``np.random``).
+
+    All pairs are drawn up front.  The reference interleaves these draws with the data-dependent ``random.sample`` of every
+    pair's matches, so its random STREAM is deliberately not replayed: only the rule is.
+
+    -> int64 array [n, 3] of (scene, frame a, frame b), frames as store indices; n <= num_image_pairs."""
+    rng = host_rng if host_rng is not None else np.random
+    first = store.scene_first_frame_host
+    multi, per_object = store.multi_scenes_host, store.object_scenes_host
+    lots = len(multi) + len(per_object)
+    if lots == 0:
+        raise ValueError("I don't think you have any scenes?")
+    t = store.translations_host
+    out = []
+    for _ in range(int(num_image_pairs)):
+        k = _below(rng, lots)
+        if k < len(multi):
+            s = multi[_below(rng, len(multi))]
+        else:
+            o = _below(rng, len(per_object))
+            scenes = per_object[o]
+            if not scenes:
+                raise ValueError("object %s has no scene in this store" % (store.object_ids[o],))
+            s = scenes[_below(rng, len(scenes))]
+        lo, cnt = first[s], first[s + 1] - first[s]
+        a = lo + _below(rng, cnt)
+        for _attempt in range(int(max_num_attempts)):
+            b = lo + _below(rng, cnt)
+            if np.linalg.norm(t[a] - t[b]) > threshold:
+                out.append((s, a, b))
+                break
+    return np.asarray(out, dtype=np.int64).reshape(-1, 3)
+
+
+def _frame_pairs(store, pairs):
+    a = np.asarray(pairs.cpu() if torch.is_tensor(pairs) else pairs)
+    if a.ndim != 2 or a.shape[1] not in (2, 3) or a.shape[0] < 1 or not np.issubdtype(a.dtype, np.integer):
+        raise ValueError("pairs must be an integer array [P, 2] of (frame a, frame b) or [P, 3] of (scene, frame a, frame b), "
+                         "P >= 1")
+    fr = a[:, -2:].astype(np.int64)
+    if fr.min() < 0 or fr.max() >= store.num_frames:
+        raise ValueError("pairs name a frame outside the store's %d frames" % store.num_frames)
+    return fr
+
+
+def evaluate_frame_pairs(dcn, store, pairs, num_matches=100, *, generator=None, draws=None, match_order=None, batch_pairs=8,
+                         mean=_aug.DEFAULT_IMAGE_MEAN, std=_aug.DEFAULT_IMAGE_STD_DEV):
+    """The reference's per-pair evaluation for ``pairs`` ([P, 2] store frame indices (a, b), or choose_pairs' [P, 3]; P <=
+    1024) on the device: 1. ``dcn_gather_frames`` of the chosen frames, 2. ToTensor + Normalize by the augmentation kernel with
+    every augmentation switched off (``mean`` / ``std``: the dataset's, as ``rgb_image_to_tensor``), 3. ``dcn.forward_image_tensors`` in eval mode, ``batch_pairs`` pairs (2 x ``batch_pairs``
+    images) at a time, 4. find_eval_matches (``draws`` / ``match_order`` replay, otherwise ``generator``), 5.
+    match_statistics_pairs.  -> EvalTable, its ``status`` covering the whole chain.  The pair list is given on the host; nothing is read back.  ``dcn.training`` is
+    left as found."""
+    fr = _frame_pairs(store, pairs)
+    P = int(fr.shape[0])
+    if P > 1024:
+        raise ValueError("at most 1024 pairs per call, got %d" % P)
+    if int(batch_pairs) < 1:
+        raise ValueError("batch_pairs must be >= 1")
+    lib = _lib.get()
+    dev = store.device
+    h, w = store.h, store.w
+    frames = torch.from_numpy(np.concatenate([fr, np.full((P, 2), -1, np.int64)], axis=1).astype(np.int32)).to(dev)
+    rgb = torch.empty((2, P, h, w, 3), dtype=torch.uint8, device=dev)
+    depth = torch.empty((2, P, h, w), dtype=torch.int16, device=dev)
+    mask = torch.empty((2, P, h, w), dtype=torch.uint8, device=dev)
+    cams = torch.empty((1, P, CAM_FLOATS), dtype=torch.float32, device=dev)
+    status = torch.zeros(1, dtype=torch.int32, device=dev)
+    p = _lib.ptr
+    rc = lib.dcn_gather_frames(P, 2, ctypes.byref(store.desc), p(frames), None, p(rgb), p(depth), p(mask), p(cams), p(status),
+                               _lib.stream_ptr())
+    _lib.check(rc, "dcn_gather_frames")
+    was_training = dcn.training
+    dcn.eval()
+    try:
+        res = [[], []]
+        step = int(batch_pairs)
+        for lo in range(0, P, step):
+            n = min(step, P - lo)
+            params = torch.zeros((2 * n, _aug.PARAM_WORDS), dtype=torch.int32, device=dev)
+            x = _aug.augment_images(rgb[0, lo:lo + n], mask[0, lo:lo + n], params, rgb_b=rgb[1, lo:lo + n],
+                                    mask_b=mask[1, lo:lo + n], mean=mean, std=std, want_mask=False)
+            y = dcn.forward_image_tensors(torch.cat([x["input_a"], x["input_b"]]))
+            res[0].append(y[:n])
+            res[1].append(y[n:])
+    finally:
+        dcn.train(was_training)
+    res_a, res_b = torch.cat(res[0]).contiguous(), torch.cat(res[1]).contiguous()
+    m = find_eval_matches(depth[0], depth[1], mask[0], cams[0], num_matches, generator=generator, draws=draws,
+                          match_order=match_order)
+    t = match_statistics_pairs(res_a, res_b, mask[1], depth[0], depth[1], cams[0], m.u_a, m.v_a, m.u_b, m.v_b, m.offsets,
+                               max_pair_rows=min(int(num_matches), NUM_ATTEMPTS))
+    # one status word for the chain (on the device): the search's BAD_DRAWS bit and the gather's BAD_INDEX bit join the table's
+    word = t.status | ((m.status >> 1) & 1) * BAD_DRAWS | (status & 1) * BAD_FRAME
+    return t._replace(status=word.to(torch.int32))
+
+
+def evaluate_network(dcn, store, num_image_pairs=25, num_matches_per_image_pair=100, host_rng=None, generator=None):
+    """``DenseCorrespondenceEvaluation.evaluate_network`` (evaluation.py:475-527) on a frame store: choose_pairs, then
+    evaluate_frame_pairs, then ONE copy to the host.  -> (table, dataframe): ``table`` a dict of numpy columns under the
+    reference's column names (COLUMNS as float64, ``is_valid`` / ``is_valid_masked`` as bool) plus ``scene_name``,
+    ``img_a_idx``, ``img_b_idx`` per row; ``dataframe`` a ``pandas.DataFrame`` of it when pandas imports, else None.  Pairs
+    without matches contribute no rows, as in the reference.  ``dcn.training`` is left as found."""
+    chosen = choose_pairs(store, num_image_pairs, host_rng)
+    names = COLUMNS + ("is_valid", "is_valid_masked", "scene_name", "img_a_idx", "img_b_idx")
+    if chosen.shape[0] == 0:
+        table = {k: np.zeros(0, np.float64) for k in COLUMNS}
+        table.update(is_valid=np.zeros(0, bool), is_valid_masked=np.zeros(0, bool), scene_name=np.zeros(0, object),
+                     img_a_idx=np.zeros(0, np.int64), img_b_idx=np.zeros(0, np.int64))
+    else:
+        t = evaluate_frame_pairs(dcn, store, chosen, num_matches_per_image_pair, generator=generator)
+        R = int(t.row_pair.numel())
+        # one transfer: everything packed into one float64 block (ints up to 2^31 are exact)
+        block = torch.cat([t.columns, t.is_valid.double(), t.row_pair.double().view(1, R)]).cpu().numpy()
+        block = block[:, :int(np.sum(block[-1] >= 0))]       # (rows past the last one carry pair -1)
+        table = {k: block[i].copy() for i, k in enumerate(COLUMNS)}
+        table["is_valid"] = block[len(COLUMNS)] != 0
+        table["is_valid_masked"] = block[len(COLUMNS) + 1] != 0
+        pair = block[len(COLUMNS) + 2].astype(np.int64)
+        first = np.asarray(store.scene_first_frame_host, np.int64)
+        scene = chosen[pair, 0]
+        table["scene_name"] = np.array([store.scene_names[s] for s in scene], dtype=object)
+        for key, col in (("img_a_idx", 1), ("img_b_idx", 2)):
+            local = chosen[pair, col] - first[scene]
+            table[key] = np.array([int(store.frame_ids[s][j]) for s, j in zip(scene, local)], dtype=np.int64)
+    assert set(table) == set(names)
+    try:
+        import pandas
+        df = pandas.DataFrame({k: table[k] for k in names})
+    except ImportError:
+        df = None
+    return table, df

@@ -79,6 +79,8 @@ class FrameStore(object):
         self.depth = (depth if depth.dtype == torch.int16 else depth.view(torch.int16)).contiguous()
         self.mask = (mask if mask.dtype == torch.uint8 else mask.to(torch.uint8)).contiguous()
         self.poses = torch.as_tensor(poses, dtype=torch.float64).to(dev).reshape(F, 16).contiguous()
+        # host copy of the frame translations, float64 [F, 3] (evaluate.choose_pairs)
+        self.translations_host = self.poses.view(F, 4, 4)[:, :3, 3].cpu().numpy().copy()
         if K is None:
             from dense_correspondence.correspondence_tools.correspondence_finder import get_default_K_matrix
             K = get_default_K_matrix()
