@@ -164,68 +164,8 @@ def _tiny_dcn(h, w):
 
 
 def test_evaluate_network_on_a_small_store():
-    h, w = 32, 48
-    store = ec.synthetic_store("cpu", h, w)
-    dcn = _tiny_dcn(h, w)
-    dcn.train()
-    run = lambda: evaluate.evaluate_network(dcn, store, num_image_pairs=6, num_matches_per_image_pair=7,
-                                            host_rng=np.random.RandomState(2), generator=torch.Generator().manual_seed(4))
-    table, df = run()
-    assert dcn.training
-    names = set(evaluate.COLUMNS) | {"is_valid", "is_valid_masked", "scene_name", "img_a_idx", "img_b_idx"}
-    assert set(table) == names
-    assert set(evaluate.COLUMNS) | {"is_valid", "is_valid_masked"} <= {
-        "is_valid", "is_valid_masked", "norm_diff_descriptor_ground_truth", "norm_diff_descriptor",
-        "norm_diff_descriptor_masked", "norm_diff_ground_truth_3d", "norm_diff_pred_3d", "norm_diff_pred_3d_masked",
-        "pixel_match_error_l2", "pixel_match_error_l2_masked", "pixel_match_error_l1",
-        "fraction_pixels_closer_than_ground_truth", "fraction_pixels_closer_than_ground_truth_masked",
-        "average_l2_distance_for_false_positives", "average_l2_distance_for_false_positives_masked"}
-    try:
-        import pandas  # noqa: F401
-        assert list(df.columns) == list(evaluate.COLUMNS) + ["is_valid", "is_valid_masked", "scene_name", "img_a_idx",
-                                                             "img_b_idx"] and len(df) == len(table["is_valid"])
-    except ImportError:
-        assert df is None
-    # the row count: sum over the chosen pairs of min(num_matches, total), from the device path run by hand
-    chosen = evaluate.choose_pairs(store, 6, np.random.RandomState(2))
-    t = evaluate.evaluate_frame_pairs(dcn, store, chosen, 7, generator=torch.Generator().manual_seed(4))
-    fb_depth = store.depth[torch.from_numpy(chosen[:, 1:])]          # [P, 2, h, w]
-    m = evaluate.find_eval_matches(fb_depth[:, 0], fb_depth[:, 1], store.mask[torch.from_numpy(chosen[:, 1])],
-                                   _cams(store, chosen), 7, generator=torch.Generator().manual_seed(4))
-    rows = int(np.minimum(m.totals.numpy(), 7).sum())
-    assert rows > 0 and len(table["is_valid"]) == rows == int(t.offsets[-1])
-    assert all(len(v) == rows for v in table.values())
-    assert np.array_equal(table["img_a_idx"], (chosen[:, 1] - np.asarray(store.scene_first_frame_host)[chosen[:, 0]])[
-        t.row_pair.numpy()])
-    assert table["scene_name"].tolist() == [store.scene_names[s] for s in chosen[t.row_pair.numpy(), 0]]
-    # deterministic for a fixed generator; eval mode is restored too
-    table2, _ = run()
-    for k in names:
-        assert np.array_equal(table[k], table2[k], equal_nan=True) if table[k].dtype != object else \
-            table[k].tolist() == table2[k].tolist(), k
-    dcn.eval()
-    run()
-    assert not dcn.training
-    # descriptors in eval mode: the first pair's best matches equal the per-pair public pieces
-    p = 0
-    a, b = int(chosen[p, 1]), int(chosen[p, 2])
-    lo, hi = int(t.offsets[p]), int(t.offsets[p + 1])
-    if hi > lo:
-        x = torch.stack([store.rgb[a], store.rgb[b]]).permute(0, 3, 1, 2).float().div(255)
-        from dcn_hip import augment
-        x = (x - torch.tensor(augment.DEFAULT_IMAGE_MEAN).view(1, 3, 1, 1)) / torch.tensor(augment.DEFAULT_IMAGE_STD_DEV).view(
-            1, 3, 1, 1)
-        res = dcn.forward_image_tensors(x)
-        from dcn_hip import match
-        q = res[0][t.v_a[lo:hi], t.u_a[lo:hi]]
-        idx, _dist, _ = match.find_best_matches(res[1], q)
-        assert torch.equal(idx % w, t.pred_uv[0, lo:hi].long()) and torch.equal(idx // w, t.pred_uv[1, lo:hi].long())
-
-
-def _cams(store, chosen):
-    from dcn_hip import samples
-    poses = store.poses.numpy().reshape(-1, 4, 4)
-    return samples._cameras(store.K[chosen[:, 0]], poses[chosen[:, 1]], poses[chosen[:, 2]], len(chosen), torch.device("cpu"))
+    import odd_size_checks as oc
+    oc.check_evaluate_on_store("cpu", 32, 48, _tiny_dcn)
 
 
 def test_error_paths():

@@ -102,7 +102,10 @@ def test_conv_rejects_bad_arguments(L):
     assert lib.dcn_conv_forward(ctypes.byref(d), None, L.ptr(t), None, L.ptr(t), None, None, None) == -1
 
 
-@pytest.mark.parametrize("shape", [(2, 4, 5, 3, 32, 40), (1, 3, 3, 16, 24, 24), (1, 6, 8, 5, 41, 59)])
+@pytest.mark.parametrize("shape", [(2, 4, 5, 3, 32, 40), (1, 3, 3, 16, 24, 24), (1, 6, 8, 5, 41, 59),
+                                   # a low-resolution map with a side of 1 (images of 8 ... 15 pixels on that side): with
+                                   # align_corners=True the scale is 0 / (H - 1) there
+                                   (1, 1, 1, 3, 8, 8), (1, 1, 2, 4, 8, 13), (2, 4, 1, 5, 29, 8)])
 def test_upsample_forward_backward(L, shape):
     lib = L.get()
     n, hl, wl, D, H, W = shape

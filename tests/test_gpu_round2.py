@@ -335,7 +335,9 @@ def test_max_pool_kernels_vs_torch_cpu(L, shape):
     assert rel_err(gx.cpu(), x.grad.permute(0, 2, 3, 1)) < 1e-6
 
 
-@pytest.mark.parametrize("shape", [(2, 60, 80, 3, 480, 640), (1, 60, 80, 16, 480, 640), (1, 120, 160, 32, 960, 1280)], ids=str)
+@pytest.mark.parametrize("shape", [(2, 60, 80, 3, 480, 640), (1, 60, 80, 16, 480, 640), (1, 120, 160, 32, 960, 1280),
+                                   # a non-integer ratio at scale (479 x 637 images), and low-resolution maps with a side of 1
+                                   (1, 60, 80, 3, 479, 637), (1, 1, 1, 3, 8, 8), (1, 1, 2, 4, 8, 13), (2, 4, 1, 5, 29, 8)], ids=str)
 @pytest.mark.parametrize("normalize", [0, 1])
 def test_upsample_kernels_vs_torch_cpu(L, shape, normalize):
     """K8 / K10 at the networks' real shapes: bilinear x8 (align_corners=True) forward (+ per-pixel L2 normalisation) and the
