@@ -36,7 +36,6 @@ struct ConvL {
     int bn = -1;
     size_t x = 0;      // conv output offset (floats) in the saved arena
     int cin_true = 0;
-    int mtiles[2] = {0, 0};   // BN partial-sum rows of the forward kernel, per conv mode
     size_t wsplit = 0;        // offset (halves) of this conv's fp16 weight image inside w_wh / w_wl (forward or dgrad image)
     size_t whl = 0;           // offset (floats) of its hl32 weight image inside w_whl (conv_hl_kernels.hip), forward or dgrad image
     bool hl_any = false;      // some launch of this convolution may take the hl32 path (an image slot is reserved)
@@ -73,6 +72,13 @@ struct ParamInfo {
     int ndim;
 };
 
+// The kernel family a launch takes -- a family, not a shape: tiles, stream-K and split counts stay with the launchers.
+// FP32: fp32 MFMA; F16: split-fp16 on fp32 operands; HL: split-fp16 on pre-split hl32 operands (big or small tile, weight
+// gradient: 256 x 256 tile or row-window kernel -- the launcher picks); STEM8: the stem's forward through the uniform-tap path
+enum class Kernel : unsigned char { FP32, F16, HL, STEM8 };
+// What one engine call does with one convolution (conv_routes)
+struct ConvRoute { Kernel fwd, dgrad, wgrad; };
+
 }  // namespace
 
 struct dcn_plan {
@@ -106,16 +112,15 @@ struct dcn_plan {
     std::vector<int> prof_cat;
     std::vector<double> prof_flops;    // algorithmic FLOPs (matrix-core categories) or HBM bytes (streaming categories)
     size_t prof_used = 0;
-    // What a training-mode forward call decided, keyed by its saved arena: the backward pass of that arena must agree with it
-    // (the tuning table or the plan's conv mode may have changed in between -- dcn_reload_env, dcn_plan_set_conv_mode -- and a
-    // backward pass that re-derived the decisions would then read tensors the forward pass never wrote)
+    // What a training-mode forward call decided, keyed by its saved arena: its route table plus the two facts that are not
+    // routes.  The tuning table or the plan's conv mode may have changed since (dcn_reload_env, dcn_plan_set_conv_mode): the
+    // backward pass of the arena compares this table with its own before it reads anything (top of backward_impl)
     struct FwdRecord {
         const void* saved = nullptr;
         int conv_mode = 0;
+        std::vector<ConvRoute> routes;
         std::vector<unsigned char> mid_hl_only;   // per convolution: its INPUT activation exists as the saved hl32 image only
-        std::vector<unsigned char> hl_x_written;  // per convolution: the saved hl32 image of its input was written
-        bool wt_saved = false;                    // the backward pass's weight images are in the saved arena (s_wht / s_wlt / s_whlt)
-        std::vector<unsigned char> hl_t_written;  // ... per convolution: its transposed hl32 image among them
+        bool wt_saved = false;   // the transposed weight images of routes[].dgrad are in the saved arena (s_wht / s_wlt / s_whlt)
     };
     // newest last; one per forward call awaiting its backward.  A record is a few hundred bytes; it is replaced by the next
     // forward call that fills the same arena and dropped when the caller says the arena is gone (dcn_plan_forget_saved: the
@@ -142,6 +147,27 @@ struct dcn_plan {
 namespace {
 
 size_t align64(size_t x) { return (x + 63) & ~size_t(63); }
+
+// The routing function: every convolution's kernel family per pass, under `conv_mode` and the tuning table of the moment.
+// Computed once at the top of each forward and backward call; everything else reads the table.  `reserving`: build_plan asks
+// which weight gradients WOULD take the hl32 kernel, before it has reserved the saved hl32 input images (has_hl_x) that follow
+// from the answer: every convolution of a block is a candidate then, and only the wgrad column of the result means anything
+std::vector<ConvRoute> conv_routes(const dcn_plan& p, int conv_mode, bool reserving = false) {
+    std::vector<ConvRoute> rt(p.convs.size(), ConvRoute{Kernel::FP32, Kernel::FP32, Kernel::FP32});
+    if (conv_mode != DCN_CONV_F16X3) return rt;
+    const dcn::Tuning& tune = dcn::tuning();
+    for (const ConvL& c : p.convs) {
+        ConvRoute& r = rt[c.idx];   // (hl_any: the plan reserved an hl32 weight-image slot; has_hl_x: a saved hl32 image of the input)
+        r.fwd = c.hl_any && dcn_conv_hl_eligible(&c.d, 0) != 0 ? Kernel::HL : Kernel::F16;
+        r.dgrad = c.hl_any && dcn_conv_hl_eligible(&c.d, 1) != 0 ? Kernel::HL : Kernel::F16;
+        const bool hl_x = reserving ? (c.idx != p.stem && c.idx != p.fc) : c.has_hl_x;
+        r.wgrad = hl_x && dcn_conv_wgrad_hl_eligible(&c.d) != 0 ? Kernel::HL : Kernel::F16;
+    }
+    const dcn_conv_desc& sd = p.convs[p.stem].d;
+    if (tune.stem8 != 0 && tune.gemm_uni != 0 && sd.win >= 8 && sd.kh == 7 && sd.cin == 4 && (int64_t)sd.n * sd.hin * sd.win * 16 <= ((int64_t)1 << 31))
+        rt[p.stem].fwd = Kernel::STEM8;
+    return rt;
+}
 
 struct Builder {
     dcn_plan& p;
@@ -186,8 +212,6 @@ struct Builder {
         c.w = add_param(name + ".weight", {cout, cin, k, k});
         if (bias) c.b = add_param(name + ".bias", {cout});
         const int64_t M = (int64_t)n * c.d.hout * c.d.wout;
-        c.mtiles[DCN_CONV_FP32] = dcn_conv_num_mtiles(&c.d);  // M tiles of the forward kernel == rows of its BN partial sums
-        c.mtiles[DCN_CONV_F16X3] = dcn_conv_num_mtiles_f16(&c.d);
         c.idx = (int)p.convs.size();
         c.flops = 2.0 * (double)M * cout * (double)(k * k * cin);
         p.flops += c.flops;
@@ -323,26 +347,21 @@ int build_plan(dcn_plan& p) {
     p.fc = B.add_conv("fc", N, h, wd, inplanes, p.D, 1, 1, 0, 1, true, p.Dp);
     p.convs[p.fc].in_act = cur_act;
     p.s_low = B.alloc_saved((size_t)N * h * wd * p.Dp);  // low-resolution descriptor map (needed by the normalise backward)
-    for (BlockL& blk : p.blocks) {   // hl32 copies of the activations whose consumer's weight gradient takes the hl32 kernel
-        for (int i = 0; i < blk.nconv; ++i) {
-            const ConvL& c = p.convs[blk.conv[i]];
-            if (!dcn_conv_wgrad_hl_eligible(&c.d)) continue;
-            const size_t fl = (size_t)c.d.n * c.d.hin * c.d.win * c.d.cin;
-            if (i == 0) { if (!blk.has_hl_in) { blk.hl_in = B.alloc_saved(fl); blk.has_hl_in = true; } }
-            else if (!blk.has_hl_mid[i - 1]) { blk.hl_mid[i - 1] = B.alloc_saved(fl); blk.has_hl_mid[i - 1] = true; }
-            p.convs[blk.conv[i]].hl_x = i == 0 ? blk.hl_in : blk.hl_mid[i - 1];
-            p.convs[blk.conv[i]].has_hl_x = true;
+    // hl32 copies of the activations whose consumer's weight gradient takes the hl32 kernel under the tuning the plan is created with
+    const std::vector<ConvRoute> want = conv_routes(p, DCN_CONV_F16X3, true);
+    for (BlockL& blk : p.blocks)
+        for (int k = 0; k < 4; ++k) {   // conv[0..2], then the downsample branch (which reads the block's input, like conv[0])
+            const int ci = k < 3 ? blk.conv[k] : blk.down;
+            if (ci < 0) continue;
+            ConvL& c = p.convs[ci];
+            c.has_hl_x = want[ci].wgrad == Kernel::HL;
+            if (!c.has_hl_x) continue;
+            const bool of_in = k == 0 || k == 3;
+            size_t& off = of_in ? blk.hl_in : blk.hl_mid[k - 1];
+            bool& has = of_in ? blk.has_hl_in : blk.has_hl_mid[k - 1];
+            if (!has) { off = B.alloc_saved((size_t)c.d.n * c.d.hin * c.d.win * c.d.cin); has = true; }
+            c.hl_x = off;
         }
-        if (blk.down >= 0 && dcn_conv_wgrad_hl_eligible(&p.convs[blk.down].d)) {
-            ConvL& c = p.convs[blk.down];
-            if (!blk.has_hl_in) {
-                blk.hl_in = B.alloc_saved((size_t)c.d.n * c.d.hin * c.d.win * c.d.cin);
-                blk.has_hl_in = true;
-            }
-            c.hl_x = blk.hl_in;
-            c.has_hl_x = true;
-        }
-    }
     p.n_act = n_act;
     p.s_actmax = B.alloc_saved((size_t)n_act + 1);        // abs-max of every convolution input (kept for wgrad) + status word
     p.saved_floats = B.saved;
@@ -528,7 +547,7 @@ struct Run {
     float* saved;
     float* ws;
     hipStream_t st;
-    bool stem8 = false;   // this call runs the stem through dcn_conv_stem_forward_f16
+    const std::vector<ConvRoute>& rt;   // this call's route table (conv_routes)
     const float* hl_src[2] = {nullptr, nullptr};   // the fp32 tensors whose hl32 images currently sit in w_hl / w_hl2
     std::vector<std::pair<const float*, const float*>> hl_saved;   // (fp32 tensor, its hl32 image in the SAVED arena) of this call
     const float* saved_hl_of(const float* t) const {
@@ -578,10 +597,11 @@ struct Run {
     // engine-level launches outside the launchers (fills, weight / operand splits, status and bias-gradient kernels)
     template <class F> int other(F&& launch) { return timed(DCN_PROF_OTHER, 0.0, launch); }
 
-    // stream-K scratch for one gather-GEMM launch, or null (no stream-K) when the tile shape selected by the tuning table
-    // of the moment needs more than the plan reserved (the table may have changed since the plan was made)
-    void* SK(const ConvL& c, int dgrad) const {
-        const size_t need = p.conv_mode == DCN_CONV_FP32 ? dcn_conv_gemm_workspace(&c.d, dgrad) : dcn_conv_gemm_workspace_f16(&c.d, dgrad);
+    // stream-K scratch for one gather-GEMM launch of family k, or null (no stream-K) when the tile shape selected by the tuning
+    // table of the moment needs more than the plan reserved (the table may have changed since the plan was made)
+    void* SK(const ConvL& c, int dgrad, Kernel k) const {
+        const size_t need = k == Kernel::FP32 ? dcn_conv_gemm_workspace(&c.d, dgrad) : k == Kernel::HL ? dcn_conv_gemm_workspace_hl(&c.d, dgrad)
+                                                                                                       : dcn_conv_gemm_workspace_f16(&c.d, dgrad);
         return need <= p.sk_bytes ? (void*)(ws + p.w_sk) : nullptr;
     }
     float* S(size_t off) const { return saved + off; }
@@ -596,18 +616,18 @@ struct Run {
     float* Wk(size_t off) const { return ws + off; }
     const float* P(int i) const { return params[i]; }
 
-    // forward convolution in the plan's conv mode (w: [cout][taps][d.cin] fp32)
+    // forward convolution on this call's route (w: [cout][taps][d.cin] fp32 -- the fp32 kernel's; split_all_weights made the others' images)
     int conv_fwd(const ConvL& c, const float* in, const float* w, const float* bias, float* out, float* part) {
-        if (p.conv_mode == DCN_CONV_FP32)
-            return timed(0, c.flops, [&] { return dcn_conv_forward(&c.d, in, w, bias, out, part, SK(c, 0), st); });
-        (void)w;   // split-fp16 mode: the image was produced by split_all_weights at the start of the call
-        if (c.idx == p.stem && stem8) {   // the 7x7 stem through the uniform-tap path (image prepared by dcn_backbone_forward)
+        const Kernel k = rt[c.idx].fwd;
+        if (k == Kernel::FP32)
+            return timed(0, c.flops, [&] { return dcn_conv_forward(&c.d, in, w, bias, out, part, SK(c, 0, k), st); });
+        if (k == Kernel::STEM8) {   // the 7x7 stem through the uniform-tap path (image prepared by dcn_backbone_forward)
             _Float16* hi = (_Float16*)Wk(p.w_stem8);
             return timed(0, c.flops, [&] {
                 return dcn_conv_stem_forward_f16(&c.d, in, A(c.in_act), hi, hi + (size_t)p.base * 224, kWeightScale, out, part, st);
             });
         }
-        if (use_hl(c, 0)) {
+        if (k == Kernel::HL) {
             // (the operand image was written by the batch-norm apply pass that produced `in` -- hl_image_for --, or is made
             // here by a stand-alone pass)
             return timed(2, c.flops, [&] {
@@ -621,12 +641,12 @@ struct Run {
                     }
                     img = hlbuf(k);
                 }
-                return dcn_conv_forward_hl(&c.d, img, A(c.in_act), whl(c), kWeightScale, bias, out, part, SKhl(c, 0), st);
+                return dcn_conv_forward_hl(&c.d, img, A(c.in_act), whl(c), kWeightScale, bias, out, part, SK(c, 0, k), st);
             });
         }
         return timed(0, c.flops, [&] {
             return dcn_conv_forward_f16(&c.d, in, A(c.in_act), wimg(p.w_wh, c), wimg(p.w_wl, c), kWeightScale, bias, out, part,
-                                        SK(c, 0), st);
+                                        SK(c, 0, k), st);
         });
     }
 
@@ -646,9 +666,6 @@ struct Run {
         return other([&] { return dcn_split_act_hl32(y, A(act), slot, rows, C, st); });
     }
     // ---- pre-split (hl32) path of the wide layers (conv_hl_kernels.hip)
-    bool use_hl(const ConvL& c, int dgrad) const {
-        return p.conv_mode == DCN_CONV_F16X3 && c.hl_any && dcn_conv_hl_eligible(&c.d, dgrad) != 0;
-    }
     void* whl(const ConvL& c) const { return (void*)((whl_over ? whl_over : Wk(p.w_whl)) + c.whl); }
     float* hlbuf(int k) const { return Wk(k == 0 ? p.w_hl : p.w_hl2); }
     // buffer k will hold the hl32 image of the activation `y` (written by the bn_apply pass that is about to produce y), if a
@@ -661,30 +678,22 @@ struct Run {
             return dcn::tuning().hl_producers != 0 ? (void*)slot : nullptr;   // (producers off: ensure_saved_hl makes it)
         }
         if (dcn::tuning().hl_producers == 0) return nullptr;
-        const bool want = (consumer_a && use_hl(*consumer_a, 0)) || (consumer_b && use_hl(*consumer_b, 0));
+        const bool want = (consumer_a && rt[consumer_a->idx].fwd == Kernel::HL) || (consumer_b && rt[consumer_b->idx].fwd == Kernel::HL);
         if (!want) return nullptr;
         hl_src[k] = y;
         return hlbuf(k);
     }
-    void* SKhl(const ConvL& c, int dgrad) const {
-        return dcn_conv_gemm_workspace_hl(&c.d, dgrad) <= p.sk_bytes ? (void*)(ws + p.w_sk) : nullptr;
-    }
     // rows of the batch-norm partial sums the forward kernel of the moment writes
     int fwd_mtiles(const ConvL& c) const {
-        if (p.conv_mode == DCN_CONV_FP32) return dcn_conv_num_mtiles(&c.d);
-        return use_hl(c, 0) ? dcn_conv_num_mtiles_hl(&c.d) : dcn_conv_num_mtiles_f16(&c.d);
-    }
-    // weight gradient on hl32 operands (wgrad_hl_kernels.hip): the plan reserved a saved hl32 image of the convolution's input
-    // (written by every training-mode forward call in the split-fp16 arithmetic)
-    bool use_wgrad_hl(const ConvL& c) const {
-        return p.conv_mode == DCN_CONV_F16X3 && c.has_hl_x && dcn_conv_wgrad_hl_eligible(&c.d) != 0;
+        const Kernel k = rt[c.idx].fwd;   // (the uniform-tap stem kernel tiles M like the split-fp16 one)
+        return k == Kernel::FP32 ? dcn_conv_num_mtiles(&c.d) : k == Kernel::HL ? dcn_conv_num_mtiles_hl(&c.d) : dcn_conv_num_mtiles_f16(&c.d);
     }
     int split_hl_weights(bool transposed) {
         std::vector<const float*> w;
         std::vector<void*> out;
         std::vector<int> cout, taps, cin, ldn;
         for (const ConvL& c : p.convs) {
-            if (!use_hl(c, transposed ? 1 : 0)) continue;
+            if ((transposed ? rt[c.idx].dgrad : rt[c.idx].fwd) != Kernel::HL) continue;
             w.push_back(P(c.w));
             out.push_back(whl(c));
             cout.push_back(c.d.cout); taps.push_back(c.d.kh * c.d.kw); cin.push_back(c.d.cin); ldn.push_back(c.d.ldc);
@@ -730,7 +739,7 @@ struct Run {
         const float* shift = S(p.bns[c.bn].stats) + p.bns[c.bn].C;
         return timed(0, c.flops, [&] {
             return dcn_conv_forward_fused_f16(&c.d, in, A(c.in_act), wimg(p.w_wh, c), wimg(p.w_wl, c), kWeightScale, shift, add,
-                                              relu, out, A(out_act), SK(c, 0), st);
+                                              relu, out, A(out_act), SK(c, 0, Kernel::F16), st);
         });
     }
 
@@ -898,7 +907,8 @@ int forward_impl(dcn_plan* plan, const float* image, const float* image_b, const
     if (!plan || !image || !params || !descriptors || !saved || !workspace) return DCN_E_INVALID;
     dcn_plan& p = *plan;
     if (image_b && p.groups != 2) return DCN_E_INVALID;
-    Run R{p, params, (float*)saved, (float*)workspace, (hipStream_t)stream};
+    const std::vector<ConvRoute> routes = conv_routes(p, p.conv_mode);
+    Run R{p, params, (float*)saved, (float*)workspace, (hipStream_t)stream, routes};
     Run::ObserverGuard observe(p);
     hipStream_t st = R.st;
     const int N = p.N;
@@ -918,7 +928,6 @@ int forward_impl(dcn_plan* plan, const float* image, const float* image_b, const
     rec.saved = saved;
     rec.conv_mode = p.conv_mode;
     rec.mid_hl_only.assign(p.convs.size(), 0);
-    rec.hl_x_written.assign(p.convs.size(), 0);
     const bool fused_eval = !training && p.conv_mode == DCN_CONV_F16X3;
     const bool f16_mode = p.conv_mode == DCN_CONV_F16X3;
     if (fused_eval) {
@@ -956,8 +965,7 @@ int forward_impl(dcn_plan* plan, const float* image, const float* image_b, const
             DCN_TRY(R.conv_fused(last, cur, res, 1, R.S(blk.out), blk.act_out));
         }
     } else {
-    const bool stem8 = p.conv_mode == DCN_CONV_F16X3 && dcn::tuning().stem8 != 0 && dcn::tuning().gemm_uni != 0 && stem.d.win >= 8 &&
-                       stem.d.kh == 7 && stem.d.cin == 4 && (int64_t)stem.d.n * stem.d.hin * stem.d.win * 16 <= ((int64_t)1 << 31);
+    const bool stem8 = routes[p.stem].fwd == Kernel::STEM8;
     // Weight images on the side stream (round 4, training, split-fp16, stem on its own image): the batched splits of ALL layers'
     // weights -- the forward images AND the channel-transposed ones of this call's backward pass, the latter into the saved arena
     // -- run next to the input layout pass, the stem convolution, its batch norm and the max pool instead of in front of them
@@ -981,7 +989,7 @@ int forward_impl(dcn_plan* plan, const float* image, const float* image_b, const
     } fork_guard{p, st};
     if (p.conv_mode == DCN_CONV_F16X3) {
         if (hoist) {
-            Run Rs{p, params, (float*)saved, (float*)workspace, p.side};
+            Run Rs{p, params, (float*)saved, (float*)workspace, p.side, routes};
             bool ok = hipEventRecord(p.ev_ws[0], st) == hipSuccess && hipStreamWaitEvent(p.side, p.ev_ws[0], 0) == hipSuccess;
             if (!ok) return DCN_E_LAUNCH;
             fork_guard.armed = true;
@@ -991,8 +999,6 @@ int forward_impl(dcn_plan* plan, const float* image, const float* image_b, const
             DCN_TRY(Rs.split_all_weights(true, nullptr));
             DCN_TRY(Rs.split_hl_weights(true));
             rec.wt_saved = true;
-            rec.hl_t_written.assign(p.convs.size(), 0);
-            for (const ConvL& c : p.convs) rec.hl_t_written[c.idx] = Rs.use_hl(c, 1) ? 1 : 0;
             if (hipEventRecord(p.ev_ws[1], p.side) != hipSuccess) return DCN_E_LAUNCH;
         } else {
             DCN_TRY(R.split_all_weights(false, R.Wk(p.w_wstem)));
@@ -1002,7 +1008,6 @@ int forward_impl(dcn_plan* plan, const float* image, const float* image_b, const
     if (stem8) {
         _Float16* hi = (_Float16*)R.Wk(p.w_stem8);
         DCN_TRY(R.other([&] { return dcn_split_stem_weights_f16(R.Wk(p.w_wstem), hi, hi + (size_t)p.base * 224, p.base, kWeightScale, st); }));
-        R.stem8 = true;
     }
     DCN_TRY(R.conv_bn(stem, R.S(p.s_in4), R.Wk(p.w_wstem), bn_running, momentum, eps, training, p.blocks[0].act_in));
     {
@@ -1027,8 +1032,6 @@ int forward_impl(dcn_plan* plan, const float* image, const float* image_b, const
         R.hl_saved.emplace_back(R.S(b0.in), R.S(b0.hl_in));
         DCN_TRY(R.other([&] { return dcn_split_act_hl32(R.S(b0.in), R.A(b0.act_in), R.S(b0.hl_in), b0.in_rows, b0.in_c, st); }));
     }
-    if (training && f16_mode)   // every saved hl32 image the plan reserved is written by this call (producers or stand-alone passes)
-        for (const ConvL& c : p.convs) rec.hl_x_written[c.idx] = c.has_hl_x ? 1 : 0;
     for (const BlockL& blk : p.blocks) {
         const float* in = R.S(blk.in);
         const float* cur = in;
@@ -1048,7 +1051,7 @@ int forward_impl(dcn_plan* plan, const float* image, const float* image_b, const
                 // the tensor's readers: the next convolution, that convolution's weight gradient (the batch norm's own backward
                 // pass takes the ReLU mask).  Both on the hl32 kernels: the image in the saved arena is the only copy written
                 const bool hl_only = hl && slot && hl == (void*)slot && (b.C % 32) == 0 && dcn::tuning().hl_only_mid != 0 &&
-                                     R.use_hl(nxt, 0) && R.use_wgrad_hl(nxt);
+                                     routes[nxt.idx].fwd == Kernel::HL && routes[nxt.idx].wgrad == Kernel::HL;
                 rec.mid_hl_only[nxt.idx] = hl_only ? 1 : 0;
                 dcn::launch_bn_apply(R.S(c.x), s, nullptr, nullptr, 1, hl_only ? nullptr : R.S(blk.mid[i]), R.M(blk.mid[i]), b.C,
                                      b.rows, p.groups, st, hl, R.A(blk.act_mid[i]));
@@ -1092,9 +1095,8 @@ int forward_impl(dcn_plan* plan, const float* image, const float* image_b, const
         return dcn::check_launch();
     }));
     if (training) {   // what the backward pass of this arena must agree with (dcn_plan::FwdRecord)
-        for (size_t i = 0; i < p.fwd_records.size();)
-            if (p.fwd_records[i].saved == saved) p.fwd_records.erase(p.fwd_records.begin() + i);
-            else ++i;
+        rec.routes = routes;
+        dcn_plan_forget_saved(&p, saved);
         if (p.fwd_records.size() >= dcn_plan::kMaxFwdRecords) p.fwd_records.erase(p.fwd_records.begin());
         p.fwd_records.push_back(std::move(rec));
     }
@@ -1127,24 +1129,27 @@ int backward_impl(dcn_plan* plan, const float* grad_descriptors, const float* gr
     if (!plan || !grad_descriptors || !params || !saved || !workspace || !grads) return DCN_E_INVALID;
     dcn_plan& p = *plan;
     if (grad_b && p.groups != 2) return DCN_E_INVALID;
-    Run R{p, params, (float*)saved, (float*)workspace, (hipStream_t)stream};
+    const std::vector<ConvRoute> routes = conv_routes(p, p.conv_mode);
+    Run R{p, params, (float*)saved, (float*)workspace, (hipStream_t)stream, routes};
     Run::ObserverGuard observe(p);
     hipStream_t st = R.st;
     const int N = p.N;
-    // the forward call that filled this arena: its decisions must still hold (see dcn_plan::FwdRecord)
-    dcn_plan::FwdRecord rec;
+    // The forward call that filled this arena (dcn_plan::FwdRecord) against this call's routes: every tensor this pass reads
+    // must have been written.  wt_have: the transposed weight images that call saved serve this pass (else: remade here)
+    bool wt_have = false;
     {
-        bool found = false;
-        for (size_t i = p.fwd_records.size(); i-- > 0;)   // (kept: the same arena may be differentiated again)
-            if (p.fwd_records[i].saved == saved) {
-                rec = p.fwd_records[i];
-                found = true;
-                break;
-            }
-        if (!found || rec.conv_mode != p.conv_mode) return DCN_E_INVALID;   // no training-mode forward of this arena, or another arithmetic
+        const dcn_plan::FwdRecord* rec = nullptr;
+        for (size_t i = p.fwd_records.size(); i-- > 0 && !rec;)   // (kept: the same arena may be differentiated again)
+            if (p.fwd_records[i].saved == saved) rec = &p.fwd_records[i];
+        if (!rec || rec->conv_mode != p.conv_mode) return DCN_E_INVALID;   // no training-mode forward of this arena, or another arithmetic
+        wt_have = rec->wt_saved;
         for (const ConvL& c : p.convs) {
-            if (R.use_wgrad_hl(c) && !rec.hl_x_written[c.idx]) return DCN_E_INVALID;    // would read an hl32 image nobody wrote
-            if (rec.mid_hl_only[c.idx] && !R.use_wgrad_hl(c)) return DCN_E_INVALID;     // would read an fp32 activation nobody wrote
+            const ConvRoute &now = routes[c.idx], &was = rec->routes[c.idx];
+            // (a split-fp16 forward writes every saved hl32 input image the plan reserved, an fp32 one none: this cannot fire once the
+            // arithmetic matches, above -- it states what the hl32 weight gradient relies on, it is no case of its own)
+            if (now.wgrad == Kernel::HL && was.wgrad == Kernel::FP32) return DCN_E_INVALID;
+            if (rec->mid_hl_only[c.idx] && now.wgrad != Kernel::HL) return DCN_E_INVALID;   // an fp32 activation nobody wrote
+            if (now.dgrad == Kernel::HL && was.dgrad != Kernel::HL) wt_have = false;   // no transposed hl32 image of this one
         }
     }
     float* part = R.Wk(p.w_part);
@@ -1203,8 +1208,8 @@ int backward_impl(dcn_plan* plan, const float* grad_descriptors, const float* gr
         // the dgrad of this convolution on the hl32 path: the apply pass writes dx as the hl32 image INSTEAD of the fp32 tensor
         // (wgrad reads the pixel-blocked image, nobody reads the fp32 one)
         const bool prod = f16 && dcn::tuning().hl_producers != 0;
-        const bool hl_d = prod && !fuse_red && R.use_hl(c, 1);       // this convolution's dgrad reads the hl32 image
-        const bool hl_w = prod && R.use_wgrad_hl(c);                  // ... its weight gradient too: no pixel-blocked image then
+        const bool hl_d = prod && !fuse_red && routes[c.idx].dgrad == Kernel::HL;   // this convolution's dgrad reads the hl32 image
+        const bool hl_w = prod && routes[c.idx].wgrad == Kernel::HL;                // ... its weight gradient too: no pixel-blocked image then
         hl_dx_of = (hl_d || hl_w) ? dx : nullptr;
         dcn::launch_bn_bwd(dy, relu_out, mask, R.S(c.x), s, R.P(b.g), b.C, b.rows, p.groups, part, grads[b.g],
                            grads[b.b], k123, dx, g_out, f16 ? amax + c.idx : nullptr,
@@ -1214,27 +1219,30 @@ int backward_impl(dcn_plan* plan, const float* grad_descriptors, const float* gr
         ++n_bn;
         dq_of = (f16 && !hl_w) ? dx : nullptr;   // the pixel-blocked split copy of this dx now sits in dqbuf[cur]
     };
+    // one weight-gradient launch reading buffer `cur`: on the side stream behind that image's writer (ev_wg[cur]: read), or in line
+    auto wgrad_launch = [&](const ConvL& c, auto&& launch) -> int {
+        if (!overlap) return R.timed(1, c.flops, [&] { return launch(st); });
+        RT(hipStreamWaitEvent(p.side, p.ev_dq[cur], 0));
+        DCN_TRY(launch(p.side));
+        RT(hipEventRecord(p.ev_wg[cur], p.side));
+        wg_pending[cur] = true;
+        return DCN_OK;
+    };
     auto wgrad = [&](const ConvL& c, const float* in, const float* dx, float* dw) -> int {
-        if (!f16) return R.timed(1, c.flops, [&] { return dcn_conv_wgrad(&c.d, in, dx, dw, slab, st); });
-        if (R.use_wgrad_hl(c)) {   // both operands as hl32 tensors: the saved image of the input, the image of dx
+        const Kernel k = routes[c.idx].wgrad;
+        if (k == Kernel::FP32) return R.timed(1, c.flops, [&] { return dcn_conv_wgrad(&c.d, in, dx, dw, slab, st); });
+        if (k == Kernel::HL) {   // both operands as hl32 tensors: the saved image of the input, the image of dx
             const float* ximg = R.S(c.hl_x);
             if (hl_dx_of != dx) {  // (DCN_HL_PRODUCERS=0, or a gradient that no batch-norm backward produced)
                 DCN_TRY(R.other([&] { return dcn_split_act_hl32(dx, amax + c.idx, hlimg[cur], (int64_t)c.d.n * c.d.hout * c.d.wout, c.d.ldc, st); }));
                 if (overlap) RT(hipEventRecord(p.ev_dq[cur], st));
                 hl_dx_of = dx;
             }
-            if (overlap) {
-                RT(hipStreamWaitEvent(p.side, p.ev_dq[cur], 0));
-                DCN_TRY(dcn_conv_wgrad_hl(&c.d, ximg, R.A(c.in_act), hlimg[cur], amax + c.idx, dw, slab, p.side));
-                RT(hipEventRecord(p.ev_wg[cur], p.side));
-                wg_pending[cur] = true;
-                return DCN_OK;
-            }
-            return R.timed(1, c.flops, [&] {
-                return dcn_conv_wgrad_hl(&c.d, ximg, R.A(c.in_act), hlimg[cur], amax + c.idx, dw, slab, st);
+            return wgrad_launch(c, [&](hipStream_t s) {
+                return dcn_conv_wgrad_hl(&c.d, ximg, R.A(c.in_act), hlimg[cur], amax + c.idx, dw, slab, s);
             });
         }
-        // The activation operand is the fp32 tensor itself, split on the fly inside the kernel: measured faster than a
+        // Kernel::F16.  The activation operand is the fp32 tensor itself, split on the fly inside the kernel: measured faster than a
         // split pass + pre-split operand on every layer of ResNet34 / ResNet50 (the pass costs more than the conversions).
         if (dq_of != dx) {   // (BN backward emits it directly; only the scoring layer's gradient needs the separate pass)
             DCN_TRY(R.other([&] { return dcn_split_grad_blocked_f16(dx, c.d.n * c.d.hout * c.d.wout, c.d.ldc, amax + c.idx, dqbuf[0], st); }));
@@ -1242,25 +1250,20 @@ int backward_impl(dcn_plan* plan, const float* grad_descriptors, const float* gr
                 return dcn_conv_wgrad_f16(&c.d, in, 1, R.A(c.in_act), dqbuf[0], amax + c.idx, dw, slab, st);
             });
         }
-        if (overlap) {
-            RT(hipStreamWaitEvent(p.side, p.ev_dq[cur], 0));
-            DCN_TRY(dcn_conv_wgrad_f16(&c.d, in, 1, R.A(c.in_act), dqbuf[cur], amax + c.idx, dw, slab, p.side));
-            RT(hipEventRecord(p.ev_wg[cur], p.side));
-            wg_pending[cur] = true;
-            return DCN_OK;
-        }
-        return R.timed(1, c.flops, [&] {
-            return dcn_conv_wgrad_f16(&c.d, in, 1, R.A(c.in_act), dqbuf[cur], amax + c.idx, dw, slab, st);
+        return wgrad_launch(c, [&](hipStream_t s) {
+            return dcn_conv_wgrad_f16(&c.d, in, 1, R.A(c.in_act), dqbuf[cur], amax + c.idx, dw, slab, s);
         });
     };
     // bn_of: the convolution whose batch norm's backward consumes din as its upstream gradient (din = gradient w.r.t. that
     // batch norm's ReLU'd output `relu_out`), or null
     auto dgrad = [&](const ConvL& c, const float* dx, const float* add, float* din, const ConvL* bn_of = nullptr,
                      const float* relu_out = nullptr) -> int {
-        if (!f16) {
+        const ConvRoute& r = routes[c.idx];
+        if (r.dgrad == Kernel::FP32) {
             DCN_TRY(R.other([&] { return dcn_transpose_weight(R.P(c.w), wt, c.d.cout, c.d.kh * c.d.kw, c.d.cin, c.d.ldc, st); }));
-            return R.timed(0, c.flops, [&] { return dcn_conv_dgrad(&c.d, dx, wt, add, din, R.SK(c, 1), st); });
+            return R.timed(0, c.flops, [&] { return dcn_conv_dgrad(&c.d, dx, wt, add, din, R.SK(c, 1, Kernel::FP32), st); });
         }
+        // (the batch-norm backward reduction in a split-fp16 dgrad's epilogue where its M tiles fit the batch norm: a tile count, asked here)
         if (fuse_red && bn_of) {
             const BnL& b = p.bns[bn_of->bn];
             const int tiles = dcn_conv_dgrad_bn_num_mtiles_f16(&c.d);
@@ -1270,11 +1273,11 @@ int backward_impl(dcn_plan* plan, const float* grad_descriptors, const float* gr
                 red_tiles = tiles / p.groups;
                 return R.timed(0, c.flops, [&] {
                     return dcn_conv_dgrad_bn_f16(&c.d, dx, R.wimg(p.w_wh, c), R.wimg(p.w_wl, c), kWeightScale, amax + c.idx, add,
-                                                 din, R.S(bn_of->x), mask, R.S(b.stats), part, R.SK(c, 1), st);
+                                                 din, R.S(bn_of->x), mask, R.S(b.stats), part, R.SK(c, 1, Kernel::F16), st);
                 });
             }
         }
-        if (R.use_hl(c, 1)) {
+        if (r.dgrad == Kernel::HL) {
             return R.timed(2, c.flops, [&] {
                 if (hl_dx_of != dx) {
                     // (the side stream's weight-gradient kernel may still be reading hlimg[cur]: the image is only rewritten when
@@ -1282,30 +1285,25 @@ int backward_impl(dcn_plan* plan, const float* grad_descriptors, const float* gr
                     DCN_TRY(dcn_split_act_hl32(dx, amax + c.idx, hlimg[cur], (int64_t)c.d.n * c.d.hout * c.d.wout, c.d.ldc, st));
                     hl_dx_of = dx;
                 }
-                return dcn_conv_dgrad_hl(&c.d, hlimg[cur], R.whl(c), kWeightScale, amax + c.idx, add, din, R.SKhl(c, 1), st);
+                return dcn_conv_dgrad_hl(&c.d, hlimg[cur], R.whl(c), kWeightScale, amax + c.idx, add, din, R.SK(c, 1, Kernel::HL), st);
             });
         }
         return R.timed(0, c.flops, [&] {   // (transposed weight images: split_all_weights(true) below)
             return dcn_conv_dgrad_f16(&c.d, dx, R.wimg(p.w_wh, c), R.wimg(p.w_wl, c), kWeightScale, amax + c.idx, add, din,
-                                      R.SK(c, 1), st);
+                                      R.SK(c, 1, Kernel::F16), st);
         });
     };
     if (f16) {
-        // the forward call of this arena already made this pass's weight images (dcn_plan::FwdRecord::wt_saved) -- unless a
-        // convolution that takes the hl32 dgrad NOW was not among them (the tuning changed in between): then they are made here
-        bool have = rec.wt_saved;
-        if (have)
-            for (const ConvL& c : p.convs)
-                if (R.use_hl(c, 1) && !rec.hl_t_written[c.idx]) have = false;
-        if (have) {
+        // the forward call of this arena already made this pass's weight images, or they are made here (wt_have, above)
+        if (wt_have) {
             R.wh_over = R.S(p.s_wht); R.wl_over = R.S(p.s_wlt); R.whl_over = R.S(p.s_whlt);
         } else {
             DCN_TRY(R.split_all_weights(true, nullptr));
             DCN_TRY(R.split_hl_weights(true));
         }
+        // every gradient tensor that feeds a convolution records its abs-max (pre-scale selection)
+        DCN_TRY(R.other([&] { return dcn::fill_bytes_async(amax, 0, p.convs.size() * sizeof(float), st); }));
     }
-    // split-fp16 mode: every gradient tensor that feeds a convolution records its abs-max (pre-scale selection)
-    if (f16) DCN_TRY(R.other([&] { return dcn::fill_bytes_async(amax, 0, p.convs.size() * sizeof(float), st); }));
 
     // ---- upsample + scoring layer
     float* glow = R.Wk(p.w_glow);

@@ -201,3 +201,28 @@ def test_hl32_eligibility_from_reduction_length_128(dcn_env):
     for d in (down4, down3, conv3):
         assert lib.dcn_conv_hl_eligible(ctypes.byref(d), 0) == 0 and lib.dcn_conv_wgrad_hl_eligible(ctypes.byref(d)) == 0
     assert lib.dcn_conv_hl_eligible(ctypes.byref(wide), 0) == 1 and lib.dcn_conv_wgrad_hl_eligible(ctypes.byref(wide)) == 1
+
+
+def test_backward_pair_is_refused_on_an_ungrouped_plan():
+    """dcn_backbone_backward_pair takes the two gradients of a forward_pair call; on a plan made for ONE batch (groups = 1) it
+    returns DCN_E_INVALID before it reads anything -- it would otherwise treat the batch as two halves.  The arena stays
+    differentiable through dcn_backbone_backward."""
+    from dcn_hip import _lib as L, backbone as bb
+    from pytorch_segmentation_detection.models import resnet_dilated as prod
+    lib = L.get()
+    m = prod.Resnet18_8s(num_classes=3, base_width=8)
+    m.train()
+    y = m(torch.randn(2, 3, 32, 40, generator=torch.Generator().manual_seed(3)))
+    node = y.grad_fn                               # the engine's autograd node
+    plan, saved, kparams = node.plan, node.saved_arena, node.kparams
+    assert plan.groups == 1
+    g = torch.ones(2, 32, 40, 3)
+    ws = bb._arena(plan.workspace_bytes, g.device)
+    flat = torch.zeros(plan.grad_offsets[-1])
+    gptr = (ctypes.c_void_p * len(plan.param_numel))(*[flat.data_ptr() + 4 * o for o in plan.grad_offsets[:-1]])
+    pptr = (ctypes.c_void_p * len(kparams))(*[p.data_ptr() for p in kparams])
+    rc = lib.dcn_backbone_backward_pair(plan.handle, L.ptr(g), L.ptr(g), pptr, L.ptr(saved), L.ptr(ws), gptr, 0, L.stream_ptr())
+    assert rc == -1                                # DCN_E_INVALID
+    assert not bool(flat.any())                    # nothing was written
+    rc = lib.dcn_backbone_backward(plan.handle, L.ptr(g), pptr, L.ptr(saved), L.ptr(ws), gptr, 0, L.stream_ptr())
+    assert rc == 0 and bool(flat.any())
