@@ -944,20 +944,95 @@ extern "C" int dcn_triplet_loss_backward(const float* desc_a, const float* desc_
     return dcn::check_launch();
 }
 
+// ------------------------------------------------------------------------------------------------ contrastive loss: entry points
 namespace {
-}  // namespace
-
-extern "C" size_t dcn_loss_workspace_bytes(int num_pairs, int64_t max_list_len) {
-    const size_t n = (size_t)4 * (size_t)num_pairs * (size_t)chunks_for(max_list_len, 0);
-    return n * sizeof(double) + (size_t)num_pairs * sizeof(double) + 2 * n * sizeof(int) + (size_t)num_pairs * sizeof(int) + 64;
+// The one place that picks a kernel instance for descriptor dimension d: calls f(Lanes<LP, SINGLE>{}) with 4 / 8 / 16 / 32
+// lanes per pixel pair, and above 32 components the 32 lanes looping over them.  Every launch site passes a generic lambda
+// that holds its hipLaunchKernelGGL and names the instance as kernel<L::lp, L::single>, L = decltype(its argument).
+template <int LP, bool SINGLE> struct Lanes {
+    static constexpr int lp = LP;
+    static constexpr bool single = SINGLE;
+};
+template <class F> void for_lanes(int d, F&& f) {
+    switch (lanes_per_pair(d)) {
+        case 4: f(Lanes<4, true>{}); break;
+        case 8: f(Lanes<8, true>{}); break;
+        case 16: f(Lanes<16, true>{}); break;
+        default:
+            if (d <= 32) f(Lanes<32, true>{});
+            else f(Lanes<32, false>{});
+            break;
+    }
 }
 
-namespace {
+// one workgroup per chunk of every list: the grid of every launch that for_lanes dispatches
+dim3 list_grid(int64_t max_list_len, int d, int num_pairs) { return dim3(chunks_for(max_list_len, d), 4 * num_pairs); }
+
+// the per-pair factors behind the n x d differences of the pair records (dcn_loss_saved_floats)
+template <class T> T* record_factors(T* pair_records, int64_t n, int d) { return pair_records ? pair_records + (size_t)n * d : nullptr; }
+
+// zero-fills the two gradient maps, in one launch where they are one allocation (dcn_hip/loss.py)
+int zero_grad_maps(float* grad_a, float* grad_b, size_t bytes, hipStream_t st) {
+    if ((char*)grad_b == (char*)grad_a + bytes) return dcn::fill_bytes_async(grad_a, 0, 2 * bytes, st) != DCN_OK ? DCN_E_LAUNCH : DCN_OK;
+    if (dcn::fill_bytes_async(grad_a, 0, bytes, st) != DCN_OK || dcn::fill_bytes_async(grad_b, 0, bytes, st) != DCN_OK) return DCN_E_LAUNCH;
+    return DCN_OK;
+}
+
+// The forward workspace of both forward entry points, stated once: n = 4 * num_pairs * chunks partials, then per pair.
+//   part_sum double[n] | pair_loss double[num_pairs] | part_cnt int[n] | part_oob int[n] | pair_flags int[num_pairs]
+struct ForwardWorkspace {
+    double *part_sum, *pair_loss;
+    int *part_cnt, *part_oob, *pair_flags;
+    ForwardWorkspace(void* workspace, int num_pairs, int chunks) {
+        const size_t n = (size_t)4 * num_pairs * chunks;
+        part_sum = (double*)workspace;
+        pair_loss = part_sum + n;
+        part_cnt = (int*)(pair_loss + num_pairs);
+        part_oob = part_cnt + n;
+        pair_flags = part_oob + n;
+    }
+    static size_t bytes(size_t num_pairs, size_t chunks) {
+        const size_t n = 4 * num_pairs * chunks;
+        return n * sizeof(double) + num_pairs * sizeof(double) + 2 * n * sizeof(int) + num_pairs * sizeof(int) + 64;
+    }
+};
+
 int loss_forward_impl(const float* desc_a, const float* desc_b, int num_pairs, int64_t hw, int d, const int64_t* idx_a,
                       const int64_t* idx_b, const int64_t* offsets_host, const int64_t* offsets_dev, const dcn_loss_config* cfg,
                       float* terms, float* sums, int32_t* hard_neg, float* loss, float* per_term, int32_t* status,
-                      void* workspace, float* rec_d, float* rec_s, void* stream);
+                      void* workspace, float* rec_d, float* rec_s, void* stream) {
+    if (!desc_a || !desc_b || !offsets_host || !offsets_dev || !cfg || !terms || !sums || !hard_neg || !loss ||
+        !status || !workspace || num_pairs < 1 || hw < 1 || d < 1)
+        return DCN_E_INVALID;
+    for (int s = 0; s < 4 * num_pairs; ++s)
+        if (offsets_host[s + 1] < offsets_host[s]) return DCN_E_INVALID;
+    if (offsets_host[4 * num_pairs] > 0 && (!idx_a || !idx_b)) return DCN_E_INVALID;
+    hipStream_t st = (hipStream_t)stream;
+    const dim3 grid = list_grid(max_len(offsets_host, num_pairs), d, num_pairs), block(kThreads);
+    const int chunks = (int)grid.x;
+    const ForwardWorkspace w(workspace, num_pairs, chunks);
+    for_lanes(d, [&](auto lanes) {
+        using L = decltype(lanes);
+        hipLaunchKernelGGL((loss_fwd_kernel<L::lp, L::single>), grid, block, 0, st, desc_a, desc_b, hw, d, idx_a, idx_b, offsets_dev,
+                           *cfg, w.part_sum, w.part_cnt, per_term, w.part_oob, rec_d, rec_s);
+    });
+    if (num_pairs <= 8) {
+        hipLaunchKernelGGL(loss_finalize_all_kernel, dim3(1), block, 0, st, w.part_sum, w.part_cnt, w.part_oob, chunks, num_pairs,
+                           offsets_dev, *cfg, terms, sums, (int*)hard_neg, w.pair_loss, loss, (int*)status);
+    } else {
+        hipLaunchKernelGGL(loss_finalize_kernel, dim3(num_pairs), block, 0, st, w.part_sum, w.part_cnt, w.part_oob, chunks,
+                           offsets_dev, *cfg, terms, sums, (int*)hard_neg, w.pair_loss, w.pair_flags);
+        hipLaunchKernelGGL(loss_mean_kernel, dim3(1), dim3(64), 0, st, (const double*)w.pair_loss, (const int*)w.pair_flags,
+                           num_pairs, loss, (int*)status);
+    }
+    return dcn::check_launch();
+}
 }  // namespace
+
+// (sized for the worst case over all d: chunks_for(.., 0))
+extern "C" size_t dcn_loss_workspace_bytes(int num_pairs, int64_t max_list_len) {
+    return ForwardWorkspace::bytes((size_t)num_pairs, (size_t)chunks_for(max_list_len, 0));
+}
 
 extern "C" int dcn_contrastive_loss_forward(const float* desc_a, const float* desc_b, int num_pairs, int64_t hw, int d,
                                             const int64_t* idx_a, const int64_t* idx_b, const int64_t* offsets_host,
@@ -978,56 +1053,10 @@ extern "C" int dcn_contrastive_loss_forward_save(const float* desc_a, const floa
                                                  float* sums, int32_t* hard_neg, float* loss, float* per_term,
                                                  int32_t* status, void* workspace, float* pair_records, void* stream) {
     if (!pair_records || !offsets_host || num_pairs < 1 || d < 1) return DCN_E_INVALID;
-    const int64_t total = offsets_host[4 * num_pairs];
     return loss_forward_impl(desc_a, desc_b, num_pairs, hw, d, idx_a, idx_b, offsets_host, offsets_dev, cfg, terms, sums, hard_neg,
-                             loss, per_term, status, workspace, pair_records, pair_records + (size_t)total * d, stream);
+                             loss, per_term, status, workspace, pair_records,
+                             record_factors(pair_records, offsets_host[4 * num_pairs], d), stream);
 }
-
-namespace {
-int loss_forward_impl(const float* desc_a, const float* desc_b, int num_pairs, int64_t hw, int d, const int64_t* idx_a,
-                      const int64_t* idx_b, const int64_t* offsets_host, const int64_t* offsets_dev, const dcn_loss_config* cfg,
-                      float* terms, float* sums, int32_t* hard_neg, float* loss, float* per_term, int32_t* status,
-                      void* workspace, float* rec_d, float* rec_s, void* stream) {
-    if (!desc_a || !desc_b || !offsets_host || !offsets_dev || !cfg || !terms || !sums || !hard_neg || !loss ||
-        !status || !workspace || num_pairs < 1 || hw < 1 || d < 1)
-        return DCN_E_INVALID;
-    for (int s = 0; s < 4 * num_pairs; ++s)
-        if (offsets_host[s + 1] < offsets_host[s]) return DCN_E_INVALID;
-    if (offsets_host[4 * num_pairs] > 0 && (!idx_a || !idx_b)) return DCN_E_INVALID;
-    hipStream_t st = (hipStream_t)stream;
-    const int chunks = chunks_for(max_len(offsets_host, num_pairs), d);
-    const size_t n = (size_t)4 * num_pairs * chunks;
-    double* part_sum = (double*)workspace;
-    double* pair_loss = part_sum + n;
-    int* part_cnt = (int*)(pair_loss + num_pairs);
-    int* part_oob = part_cnt + n;
-    int* pair_oob = part_oob + n;
-    const dim3 grid(chunks, 4 * num_pairs), block(kThreads);
-#define DCN_LAUNCH_FWD(LP, SINGLE)                                                                                       \
-    hipLaunchKernelGGL((loss_fwd_kernel<LP, SINGLE>), grid, block, 0, st, desc_a, desc_b, hw, d, idx_a, idx_b, offsets_dev, \
-                       *cfg, part_sum, part_cnt, per_term, part_oob, rec_d, rec_s)
-    switch (lanes_per_pair(d)) {
-        case 4: DCN_LAUNCH_FWD(4, true); break;
-        case 8: DCN_LAUNCH_FWD(8, true); break;
-        case 16: DCN_LAUNCH_FWD(16, true); break;
-        default:
-            if (d <= 32) DCN_LAUNCH_FWD(32, true);
-            else DCN_LAUNCH_FWD(32, false);
-            break;
-    }
-#undef DCN_LAUNCH_FWD
-    if (num_pairs <= 8) {
-        hipLaunchKernelGGL(loss_finalize_all_kernel, dim3(1), block, 0, st, part_sum, part_cnt, part_oob, chunks, num_pairs,
-                           offsets_dev, *cfg, terms, sums, (int*)hard_neg, pair_loss, loss, (int*)status);
-    } else {
-        hipLaunchKernelGGL(loss_finalize_kernel, dim3(num_pairs), block, 0, st, part_sum, part_cnt, part_oob, chunks, offsets_dev,
-                           *cfg, terms, sums, (int*)hard_neg, pair_loss, pair_oob);
-        hipLaunchKernelGGL(loss_mean_kernel, dim3(1), dim3(64), 0, st, (const double*)pair_loss, (const int*)pair_oob, num_pairs,
-                           loss, (int*)status);
-    }
-    return dcn::check_launch();
-}
-}  // namespace
 
 extern "C" int dcn_contrastive_loss_backward(const float* desc_a, const float* desc_b, int num_pairs, int64_t hw, int d,
                                              const int64_t* idx_a, const int64_t* idx_b, const int64_t* offsets_host,
@@ -1040,29 +1069,15 @@ extern "C" int dcn_contrastive_loss_backward(const float* desc_a, const float* d
         return DCN_E_INVALID;
     if (!pair_grad && (!hard_neg || !grad_loss)) return DCN_E_INVALID;
     hipStream_t st = (hipStream_t)stream;
-    const size_t bytes = (size_t)num_pairs * (size_t)hw * (size_t)d * sizeof(float);
-    if ((char*)grad_b == (char*)grad_a + bytes) {   // the two maps are one allocation (dcn_hip/loss.py): one fill launch
-        if (dcn::fill_bytes_async(grad_a, 0, 2 * bytes, st) != DCN_OK) return DCN_E_LAUNCH;
-    } else {
-        if (dcn::fill_bytes_async(grad_a, 0, bytes, st) != DCN_OK) return DCN_E_LAUNCH;
-        if (dcn::fill_bytes_async(grad_b, 0, bytes, st) != DCN_OK) return DCN_E_LAUNCH;
-    }
+    if (zero_grad_maps(grad_a, grad_b, (size_t)num_pairs * (size_t)hw * (size_t)d * sizeof(float), st) != DCN_OK) return DCN_E_LAUNCH;
     const int64_t ml = max_len(offsets_host, num_pairs);
     if (ml == 0) return DCN_OK;
-    const dim3 grid(chunks_for(ml, d), 4 * num_pairs), block(kThreads);
-#define DCN_LAUNCH_BWD(LP, SINGLE)                                                                                        \
-    hipLaunchKernelGGL((loss_bwd_kernel<LP, SINGLE>), grid, block, 0, st, desc_a, desc_b, hw, d, num_pairs, idx_a, idx_b,   \
-                       offsets_dev, *cfg, (const int*)hard_neg, grad_loss, pair_grad, grad_a, grad_b)
-    switch (lanes_per_pair(d)) {
-        case 4: DCN_LAUNCH_BWD(4, true); break;
-        case 8: DCN_LAUNCH_BWD(8, true); break;
-        case 16: DCN_LAUNCH_BWD(16, true); break;
-        default:
-            if (d <= 32) DCN_LAUNCH_BWD(32, true);
-            else DCN_LAUNCH_BWD(32, false);
-            break;
-    }
-#undef DCN_LAUNCH_BWD
+    const dim3 grid = list_grid(ml, d, num_pairs), block(kThreads);
+    for_lanes(d, [&](auto lanes) {
+        using L = decltype(lanes);
+        hipLaunchKernelGGL((loss_bwd_kernel<L::lp, L::single>), grid, block, 0, st, desc_a, desc_b, hw, d, num_pairs, idx_a, idx_b,
+                           offsets_dev, *cfg, (const int*)hard_neg, grad_loss, pair_grad, grad_a, grad_b);
+    });
     return dcn::check_launch();
 }
 
@@ -1078,35 +1093,18 @@ extern "C" int dcn_contrastive_loss_backward_saved(int num_pairs, int64_t hw, in
         hw < 1 || d < 1)
         return DCN_E_INVALID;
     hipStream_t st = (hipStream_t)stream;
-    const size_t bytes = (size_t)num_pairs * (size_t)hw * (size_t)d * sizeof(float);
-    if (!prefilled) {
-        if ((char*)grad_b == (char*)grad_a + bytes) {
-            if (dcn::fill_bytes_async(grad_a, 0, 2 * bytes, st) != DCN_OK) return DCN_E_LAUNCH;
-        } else {
-            if (dcn::fill_bytes_async(grad_a, 0, bytes, st) != DCN_OK) return DCN_E_LAUNCH;
-            if (dcn::fill_bytes_async(grad_b, 0, bytes, st) != DCN_OK) return DCN_E_LAUNCH;
-        }
-    }
+    if (!prefilled && zero_grad_maps(grad_a, grad_b, (size_t)num_pairs * (size_t)hw * (size_t)d * sizeof(float), st) != DCN_OK)
+        return DCN_E_LAUNCH;
     const int64_t ml = max_len(offsets_host, num_pairs);
     if (ml == 0) return DCN_OK;
     if (!idx_a || !idx_b) return DCN_E_INVALID;
-    const int64_t total = offsets_host[4 * num_pairs];
-    const float* rec_d = pair_records;
-    const float* rec_s = pair_records + (size_t)total * d;
-    const dim3 grid(chunks_for(ml, d), 4 * num_pairs), block(kThreads);
-#define DCN_LAUNCH_BWDS(LP, SINGLE)                                                                                          \
-    hipLaunchKernelGGL((loss_bwd_saved_kernel<LP, SINGLE>), grid, block, 0, st, hw, d, num_pairs, idx_a, idx_b, offsets_dev, *cfg, \
-                       (const int*)hard_neg, grad_loss, rec_d, rec_s, grad_a, grad_b)
-    switch (lanes_per_pair(d)) {
-        case 4: DCN_LAUNCH_BWDS(4, true); break;
-        case 8: DCN_LAUNCH_BWDS(8, true); break;
-        case 16: DCN_LAUNCH_BWDS(16, true); break;
-        default:
-            if (d <= 32) DCN_LAUNCH_BWDS(32, true);
-            else DCN_LAUNCH_BWDS(32, false);
-            break;
-    }
-#undef DCN_LAUNCH_BWDS
+    const float* rec_s = record_factors(pair_records, offsets_host[4 * num_pairs], d);
+    const dim3 grid = list_grid(ml, d, num_pairs), block(kThreads);
+    for_lanes(d, [&](auto lanes) {
+        using L = decltype(lanes);
+        hipLaunchKernelGGL((loss_bwd_saved_kernel<L::lp, L::single>), grid, block, 0, st, hw, d, num_pairs, idx_a, idx_b, offsets_dev,
+                           *cfg, (const int*)hard_neg, grad_loss, pair_records, rec_s, grad_a, grad_b);
+    });
     return dcn::check_launch();
 }
 
@@ -1115,6 +1113,33 @@ extern "C" size_t dcn_loss_exact_workspace_bytes(int num_pairs, int64_t hw, int 
     if (num_pairs < 1 || hw < 1 || d < 1) return 0;
     return (size_t)2 * num_pairs * (size_t)hw * d * sizeof(long long) + (((size_t)num_pairs * 4 + 255) / 256) * 256;
 }
+
+namespace {
+// that workspace: accA | accB | vmax
+struct ExactWorkspace {
+    unsigned long long *accA, *accB;
+    float* vmax;
+};
+
+// carves the exact backward's workspace and zero-fills all of it
+int exact_begin(void* workspace, int num_pairs, int64_t hw, int d, hipStream_t st, ExactWorkspace* w) {
+    const size_t map = (size_t)num_pairs * (size_t)hw * d;
+    w->accA = (unsigned long long*)workspace;
+    w->accB = w->accA + map;
+    w->vmax = (float*)(w->accB + map);
+    return dcn::fill_bytes_async(workspace, 0, dcn_loss_exact_workspace_bytes(num_pairs, hw, d), st) != DCN_OK ? DCN_E_LAUNCH : DCN_OK;
+}
+
+// the accumulated fixed-point maps to the two float gradient maps (written in full)
+int exact_finish(const ExactWorkspace& w, int num_pairs, int64_t hw, int d, float* grad_a, float* grad_b, hipStream_t st) {
+    const int64_t per_pair = hw * d;
+    const unsigned bx = (unsigned)std::max<int64_t>(1, std::min<int64_t>(dcn::ceil_div64(per_pair / 2 + 1, 256 * 4),
+                                                                         (256 * 16) / (2 * num_pairs) + 1));
+    hipLaunchKernelGGL(loss_exact_convert_kernel, dim3(bx, 2 * num_pairs), dim3(256), 0, st, (const long long*)w.accA,
+                       (const float*)w.vmax, grad_a, grad_b, per_pair, num_pairs);
+    return dcn::check_launch();
+}
+}  // namespace
 
 // dcn_contrastive_loss_backward_saved with bit-reproducible gradient maps (64-bit fixed-point accumulation under a per-pair
 // power-of-two scale; see loss_bwd_saved_exact_kernel).  grad_a / grad_b are written in full (no zero-fill needed).
@@ -1132,41 +1157,23 @@ extern "C" int dcn_contrastive_loss_backward_saved_exact(int num_pairs, int64_t 
     for (int p = 0; p < num_pairs; ++p)
         if (offsets_host[4 * p + 4] - offsets_host[4 * p] >= ((int64_t)1 << 22)) return DCN_E_UNSUPPORTED;
     hipStream_t st = (hipStream_t)stream;
-    const size_t per_pair = (size_t)hw * d, map_bytes = (size_t)num_pairs * per_pair * sizeof(long long);
-    unsigned long long* accA = (unsigned long long*)workspace;
-    unsigned long long* accB = accA + (size_t)num_pairs * per_pair;
-    float* vmax = (float*)((char*)workspace + 2 * map_bytes);
-    if (dcn::fill_bytes_async(workspace, 0, dcn_loss_exact_workspace_bytes(num_pairs, hw, d), st) != DCN_OK) return DCN_E_LAUNCH;
+    ExactWorkspace w;
+    if (exact_begin(workspace, num_pairs, hw, d, st, &w) != DCN_OK) return DCN_E_LAUNCH;
     const int64_t ml = max_len(offsets_host, num_pairs);
     if (ml > 0) {
         if (!idx_a || !idx_b) return DCN_E_INVALID;
-        const int64_t total = offsets_host[4 * num_pairs];
-        const float* rec_d = pair_records;
-        const float* rec_s = pair_records + (size_t)total * d;
-        const dim3 grid(chunks_for(ml, d), 4 * num_pairs), block(kThreads);
-#define DCN_LAUNCH_BWDX(LP, SINGLE)                                                                                          \
-        do {                                                                                                                  \
-            hipLaunchKernelGGL((loss_bwd_vmax_kernel<LP, SINGLE>), grid, block, 0, st, d, num_pairs, offsets_dev, *cfg,       \
-                               (const int*)hard_neg, grad_loss, rec_d, rec_s, (unsigned*)vmax);                              \
-            hipLaunchKernelGGL((loss_bwd_saved_exact_kernel<LP, SINGLE>), grid, block, 0, st, hw, d, num_pairs, idx_a, idx_b, \
-                               offsets_dev, *cfg, (const int*)hard_neg, grad_loss, rec_d, rec_s, (const float*)vmax, accA, accB); \
-        } while (0)
-        switch (lanes_per_pair(d)) {
-            case 4: DCN_LAUNCH_BWDX(4, true); break;
-            case 8: DCN_LAUNCH_BWDX(8, true); break;
-            case 16: DCN_LAUNCH_BWDX(16, true); break;
-            default:
-                if (d <= 32) DCN_LAUNCH_BWDX(32, true);
-                else DCN_LAUNCH_BWDX(32, false);
-                break;
-        }
-#undef DCN_LAUNCH_BWDX
+        const float* rec_s = record_factors(pair_records, offsets_host[4 * num_pairs], d);
+        const dim3 grid = list_grid(ml, d, num_pairs), block(kThreads);
+        for_lanes(d, [&](auto lanes) {
+            using L = decltype(lanes);
+            hipLaunchKernelGGL((loss_bwd_vmax_kernel<L::lp, L::single>), grid, block, 0, st, d, num_pairs, offsets_dev, *cfg,
+                               (const int*)hard_neg, grad_loss, pair_records, rec_s, (unsigned*)w.vmax);
+            hipLaunchKernelGGL((loss_bwd_saved_exact_kernel<L::lp, L::single>), grid, block, 0, st, hw, d, num_pairs, idx_a, idx_b,
+                               offsets_dev, *cfg, (const int*)hard_neg, grad_loss, pair_records, rec_s, (const float*)w.vmax,
+                               w.accA, w.accB);
+        });
     }
-    const unsigned bx = (unsigned)std::max<int64_t>(1, std::min<int64_t>(dcn::ceil_div64((int64_t)per_pair / 2 + 1, 256 * 4),
-                                                                         (256 * 16) / (2 * num_pairs) + 1));
-    hipLaunchKernelGGL(loss_exact_convert_kernel, dim3(bx, 2 * num_pairs), dim3(256), 0, st, (const long long*)workspace,
-                       (const float*)vmax, grad_a, grad_b, (int64_t)per_pair, num_pairs);
-    return dcn::check_launch();
+    return exact_finish(w, num_pairs, hw, d, grad_a, grad_b, st);
 }
 
 // ------------------------------------------------------------------------------------------------ mixed data types: entry points
@@ -1204,36 +1211,22 @@ extern "C" int dcn_contrastive_loss_mixed_forward(const float* desc_a, const flo
     if (rc != DCN_OK) return rc;
     if (!desc_a || !desc_b || !terms || !sums || !hard_neg || !loss || !num_valid || !status || !workspace) return DCN_E_INVALID;
     hipStream_t st = (hipStream_t)stream;
-    const int chunks = chunks_for(m.max_list_len, d);
-    const size_t n = (size_t)4 * num_pairs * chunks;
-    double* part_sum = (double*)workspace;                           // (the layout of loss_forward_impl)
-    double* pair_loss = part_sum + n;
-    int* part_cnt = (int*)(pair_loss + num_pairs);
-    int* part_oob = part_cnt + n;
-    int* pair_flags = part_oob + n;
-    float* rec_d = pair_records;
-    float* rec_s = pair_records ? pair_records + (size_t)capacity * d : nullptr;
-    const dim3 grid(chunks, 4 * num_pairs), block(kThreads);
-#define DCN_LAUNCH_FWDM(LP, SINGLE)                                                                                        \
-    hipLaunchKernelGGL((loss_fwd_mixed_kernel<LP, SINGLE>), grid, block, 0, st, desc_a, desc_b, hw, d, idx_a, idx_b, m, tab, \
-                       part_sum, part_cnt, part_oob, rec_d, rec_s)
-    switch (lanes_per_pair(d)) {
-        case 4: DCN_LAUNCH_FWDM(4, true); break;
-        case 8: DCN_LAUNCH_FWDM(8, true); break;
-        case 16: DCN_LAUNCH_FWDM(16, true); break;
-        default:
-            if (d <= 32) DCN_LAUNCH_FWDM(32, true);
-            else DCN_LAUNCH_FWDM(32, false);
-            break;
-    }
-#undef DCN_LAUNCH_FWDM
+    const dim3 grid = list_grid(m.max_list_len, d, num_pairs), block(kThreads);
+    const int chunks = (int)grid.x;
+    const ForwardWorkspace w(workspace, num_pairs, chunks);
+    float* rec_s = record_factors(pair_records, capacity, d);
+    for_lanes(d, [&](auto lanes) {
+        using L = decltype(lanes);
+        hipLaunchKernelGGL((loss_fwd_mixed_kernel<L::lp, L::single>), grid, block, 0, st, desc_a, desc_b, hw, d, idx_a, idx_b, m, tab,
+                           w.part_sum, w.part_cnt, w.part_oob, pair_records, rec_s);
+    });
     if (num_pairs <= 8) {
-        hipLaunchKernelGGL(loss_finalize_all_mixed_kernel, dim3(1), block, 0, st, part_sum, part_cnt, part_oob, chunks, m, tab,
-                           terms, sums, (int*)hard_neg, pair_loss, loss, (int*)num_valid, (int*)status);
+        hipLaunchKernelGGL(loss_finalize_all_mixed_kernel, dim3(1), block, 0, st, w.part_sum, w.part_cnt, w.part_oob, chunks, m, tab,
+                           terms, sums, (int*)hard_neg, w.pair_loss, loss, (int*)num_valid, (int*)status);
     } else {
-        hipLaunchKernelGGL(loss_finalize_mixed_kernel, dim3(num_pairs), block, 0, st, part_sum, part_cnt, part_oob, chunks, m, tab,
-                           terms, sums, (int*)hard_neg, pair_loss, pair_flags);
-        hipLaunchKernelGGL(loss_mean_mixed_kernel, dim3(1), dim3(64), 0, st, (const double*)pair_loss, (const int*)pair_flags, m,
+        hipLaunchKernelGGL(loss_finalize_mixed_kernel, dim3(num_pairs), block, 0, st, w.part_sum, w.part_cnt, w.part_oob, chunks, m,
+                           tab, terms, sums, (int*)hard_neg, w.pair_loss, w.pair_flags);
+        hipLaunchKernelGGL(loss_mean_mixed_kernel, dim3(1), dim3(64), 0, st, (const double*)w.pair_loss, (const int*)w.pair_flags, m,
                            loss, (int*)num_valid, (int*)status);
     }
     return dcn::check_launch();
@@ -1253,33 +1246,17 @@ extern "C" int dcn_contrastive_loss_mixed_backward_saved(int num_pairs, int64_t 
     if (rc != DCN_OK) return rc;
     if (!hard_neg || !num_valid || !grad_loss || !grad_a || !grad_b) return DCN_E_INVALID;
     hipStream_t st = (hipStream_t)stream;
-    const size_t bytes = (size_t)num_pairs * (size_t)hw * (size_t)d * sizeof(float);
-    if (!prefilled) {
-        if ((char*)grad_b == (char*)grad_a + bytes) {
-            if (dcn::fill_bytes_async(grad_a, 0, 2 * bytes, st) != DCN_OK) return DCN_E_LAUNCH;
-        } else {
-            if (dcn::fill_bytes_async(grad_a, 0, bytes, st) != DCN_OK) return DCN_E_LAUNCH;
-            if (dcn::fill_bytes_async(grad_b, 0, bytes, st) != DCN_OK) return DCN_E_LAUNCH;
-        }
-    }
+    if (!prefilled && zero_grad_maps(grad_a, grad_b, (size_t)num_pairs * (size_t)hw * (size_t)d * sizeof(float), st) != DCN_OK)
+        return DCN_E_LAUNCH;
     if (m.max_list_len == 0) return DCN_OK;
     if (!pair_records) return DCN_E_INVALID;
-    const float* rec_d = pair_records;
-    const float* rec_s = pair_records + (size_t)capacity * d;
-    const dim3 grid(chunks_for(m.max_list_len, d), 4 * num_pairs), block(kThreads);
-#define DCN_LAUNCH_BWDSM(LP, SINGLE)                                                                                          \
-    hipLaunchKernelGGL((loss_bwd_saved_mixed_kernel<LP, SINGLE>), grid, block, 0, st, hw, d, idx_a, idx_b, m, tab,             \
-                       (const int*)hard_neg, (const int*)num_valid, grad_loss, rec_d, rec_s, grad_a, grad_b)
-    switch (lanes_per_pair(d)) {
-        case 4: DCN_LAUNCH_BWDSM(4, true); break;
-        case 8: DCN_LAUNCH_BWDSM(8, true); break;
-        case 16: DCN_LAUNCH_BWDSM(16, true); break;
-        default:
-            if (d <= 32) DCN_LAUNCH_BWDSM(32, true);
-            else DCN_LAUNCH_BWDSM(32, false);
-            break;
-    }
-#undef DCN_LAUNCH_BWDSM
+    const float* rec_s = record_factors(pair_records, capacity, d);
+    const dim3 grid = list_grid(m.max_list_len, d, num_pairs), block(kThreads);
+    for_lanes(d, [&](auto lanes) {
+        using L = decltype(lanes);
+        hipLaunchKernelGGL((loss_bwd_saved_mixed_kernel<L::lp, L::single>), grid, block, 0, st, hw, d, idx_a, idx_b, m, tab,
+                           (const int*)hard_neg, (const int*)num_valid, grad_loss, pair_records, rec_s, grad_a, grad_b);
+    });
     return dcn::check_launch();
 }
 
@@ -1299,40 +1276,22 @@ extern "C" int dcn_contrastive_loss_mixed_backward_saved_exact(int num_pairs, in
     // the headroom of the 63-bit sums, from the host bound: the kernels leave out any pair with more entries than that
     if (m.max_pair_len >= ((int64_t)1 << 22)) return DCN_E_UNSUPPORTED;
     hipStream_t st = (hipStream_t)stream;
-    const size_t per_pair = (size_t)hw * d, map_bytes = (size_t)num_pairs * per_pair * sizeof(long long);
-    unsigned long long* accA = (unsigned long long*)workspace;
-    unsigned long long* accB = accA + (size_t)num_pairs * per_pair;
-    float* vmax = (float*)((char*)workspace + 2 * map_bytes);
-    if (dcn::fill_bytes_async(workspace, 0, dcn_loss_exact_workspace_bytes(num_pairs, hw, d), st) != DCN_OK) return DCN_E_LAUNCH;
+    ExactWorkspace w;
+    if (exact_begin(workspace, num_pairs, hw, d, st, &w) != DCN_OK) return DCN_E_LAUNCH;
     if (m.max_list_len > 0) {
         if (!pair_records) return DCN_E_INVALID;
-        const float* rec_d = pair_records;
-        const float* rec_s = pair_records + (size_t)capacity * d;
-        const dim3 grid(chunks_for(m.max_list_len, d), 4 * num_pairs), block(kThreads);
-#define DCN_LAUNCH_BWDXM(LP, SINGLE)                                                                                          \
-        do {                                                                                                                  \
-            hipLaunchKernelGGL((loss_bwd_vmax_mixed_kernel<LP, SINGLE>), grid, block, 0, st, d, m, tab, (const int*)hard_neg,  \
-                               (const int*)num_valid, grad_loss, rec_d, rec_s, (unsigned*)vmax);                              \
-            hipLaunchKernelGGL((loss_bwd_saved_exact_mixed_kernel<LP, SINGLE>), grid, block, 0, st, hw, d, idx_a, idx_b, m, tab, \
-                               (const int*)hard_neg, (const int*)num_valid, grad_loss, rec_d, rec_s, (const float*)vmax, accA, \
-                               accB);                                                                                         \
-        } while (0)
-        switch (lanes_per_pair(d)) {
-            case 4: DCN_LAUNCH_BWDXM(4, true); break;
-            case 8: DCN_LAUNCH_BWDXM(8, true); break;
-            case 16: DCN_LAUNCH_BWDXM(16, true); break;
-            default:
-                if (d <= 32) DCN_LAUNCH_BWDXM(32, true);
-                else DCN_LAUNCH_BWDXM(32, false);
-                break;
-        }
-#undef DCN_LAUNCH_BWDXM
+        const float* rec_s = record_factors(pair_records, capacity, d);
+        const dim3 grid = list_grid(m.max_list_len, d, num_pairs), block(kThreads);
+        for_lanes(d, [&](auto lanes) {
+            using L = decltype(lanes);
+            hipLaunchKernelGGL((loss_bwd_vmax_mixed_kernel<L::lp, L::single>), grid, block, 0, st, d, m, tab, (const int*)hard_neg,
+                               (const int*)num_valid, grad_loss, pair_records, rec_s, (unsigned*)w.vmax);
+            hipLaunchKernelGGL((loss_bwd_saved_exact_mixed_kernel<L::lp, L::single>), grid, block, 0, st, hw, d, idx_a, idx_b, m, tab,
+                               (const int*)hard_neg, (const int*)num_valid, grad_loss, pair_records, rec_s, (const float*)w.vmax,
+                               w.accA, w.accB);
+        });
     }
-    const unsigned bx = (unsigned)std::max<int64_t>(1, std::min<int64_t>(dcn::ceil_div64((int64_t)per_pair / 2 + 1, 256 * 4),
-                                                                         (256 * 16) / (2 * num_pairs) + 1));
-    hipLaunchKernelGGL(loss_exact_convert_kernel, dim3(bx, 2 * num_pairs), dim3(256), 0, st, (const long long*)workspace,
-                       (const float*)vmax, grad_a, grad_b, (int64_t)per_pair, num_pairs);
-    return dcn::check_launch();
+    return exact_finish(w, num_pairs, hw, d, grad_a, grad_b, st);
 }
 
 // Stream-ordered fill of n bytes (n % 4 == 0) with a byte value, as a kernel (an ordinary node under hipGraph capture).

@@ -35,6 +35,7 @@ class PairLists(object):
         self._off_c = (ctypes.c_int64 * len(self.offsets_host))(*self.offsets_host)
         self.offsets_dev = torch.tensor(self.offsets_host, dtype=torch.int64).to(idx_a.device, non_blocking=True)
         self.max_len = max([self.offsets_host[i + 1] - self.offsets_host[i] for i in range(4 * self.num_pairs)] + [0])
+        self.max_pair_len = max([self.offsets_host[4 * p + 4] - self.offsets_host[4 * p] for p in range(self.num_pairs)] + [0])
         self.total = self.offsets_host[-1]
 
     @staticmethod
@@ -114,39 +115,53 @@ def _fill_stream(dev):
     return st
 
 
-def _run_forward(desc_a, desc_b, lists, cfg, want_per_term, records=None):
-    lib = _lib.get()
-    _lib.require_device(desc_a, desc_b, lists.idx_a, lists.idx_b)
-    P, HW, D = desc_a.shape
+def _check_maps(desc_a, desc_b, num_pairs):
+    """The two descriptor maps of a forward call, contiguous: float32 [num_pairs, HW, D], both of one shape."""
     if desc_a.dtype != torch.float32 or desc_b.dtype != torch.float32:
         raise TypeError("dcn_hip loss kernels take float32 descriptor maps, got %s / %s (cast with .float(); the gradient "
                         "then flows back through the cast)" % (desc_a.dtype, desc_b.dtype))
-    if desc_b.shape != desc_a.shape or P != lists.num_pairs:
+    if desc_a.dim() != 3 or desc_b.shape != desc_a.shape or int(desc_a.shape[0]) != num_pairs:
         raise ValueError("descriptor maps %s / %s do not match %d pair lists" %
-                         (tuple(desc_a.shape), tuple(desc_b.shape), lists.num_pairs))
-    desc_a = desc_a.contiguous()
-    desc_b = desc_b.contiguous()
+                         (tuple(desc_a.shape), tuple(desc_b.shape), num_pairs))
+    return desc_a.contiguous(), desc_b.contiguous()
+
+
+def _small_outputs(P, dev):
+    """terms [P, 5], sums [P, 4], hard_neg int32 [P, 4], loss [1], status int32 [1] of a forward call"""
+    f32, i32 = dict(dtype=torch.float32, device=dev), dict(dtype=torch.int32, device=dev)
+    return torch.empty(P, 5, **f32), torch.empty(P, 4, **f32), torch.empty(P, 4, **i32), torch.empty(1, **f32), torch.empty(1, **i32)
+
+
+def _use_exact(exact_bytes, max_pair_len, num_pairs):
+    """The order-independent backward: where EXACT_BACKWARD forces it, else where its workspace stays below
+    EXACT_BACKWARD_MAX_BYTES -- and either way only inside what the exact entry points take (DCN_E_UNSUPPORTED beyond).
+    (The pair count never decides for DeviceLists: the mixed forward refuses more than 16383 pairs, so no mixed backward with
+    more exists.)"""
+    wanted = EXACT_BACKWARD if EXACT_BACKWARD is not None else exact_bytes <= EXACT_BACKWARD_MAX_BYTES
+    return wanted and max_pair_len < (1 << 22) and num_pairs <= 16383
+
+
+def _list_args(lists, cfg):
+    """idx_a, idx_b, offsets_host, offsets_dev, cfg: the run of arguments every PairLists entry point takes"""
+    return (_lib.ptr(lists.idx_a), _lib.ptr(lists.idx_b), ctypes.cast(lists._off_c, ctypes.c_void_p),
+            _lib.ptr(lists.offsets_dev), ctypes.byref(cfg))
+
+
+def _run_forward(desc_a, desc_b, lists, cfg, want_per_term, records=None):
+    lib = _lib.get()
+    _lib.require_device(desc_a, desc_b, lists.idx_a, lists.idx_b)
+    desc_a, desc_b = _check_maps(desc_a, desc_b, lists.num_pairs)
+    P, HW, D = desc_a.shape
     dev = desc_a.device
-    f32 = dict(dtype=torch.float32, device=dev)
-    terms = torch.empty(P, 5, **f32)
-    sums = torch.empty(P, 4, **f32)
-    hard = torch.empty(P, 4, dtype=torch.int32, device=dev)
-    loss = torch.empty(1, **f32)
-    status = torch.empty(1, dtype=torch.int32, device=dev)
-    per_term = torch.empty(max(lists.total, 1), **f32) if want_per_term else None
+    terms, sums, hard, loss, status = _small_outputs(P, dev)
+    per_term = torch.empty(max(lists.total, 1), dtype=torch.float32, device=dev) if want_per_term else None
     ws = torch.empty(lib.dcn_loss_workspace_bytes(P, lists.max_len), dtype=torch.uint8, device=dev)
+    args = (_lib.ptr(desc_a), _lib.ptr(desc_b), P, HW, D) + _list_args(lists, cfg) + (
+        _lib.ptr(terms), _lib.ptr(sums), _lib.ptr(hard), _lib.ptr(loss), _lib.ptr(per_term), _lib.ptr(status), _lib.ptr(ws))
     if records is not None:
-        rc = lib.dcn_contrastive_loss_forward_save(
-            _lib.ptr(desc_a), _lib.ptr(desc_b), P, HW, D, _lib.ptr(lists.idx_a), _lib.ptr(lists.idx_b),
-            ctypes.cast(lists._off_c, ctypes.c_void_p), _lib.ptr(lists.offsets_dev), ctypes.byref(cfg),
-            _lib.ptr(terms), _lib.ptr(sums), _lib.ptr(hard), _lib.ptr(loss), _lib.ptr(per_term), _lib.ptr(status),
-            _lib.ptr(ws), _lib.ptr(records), _lib.stream_ptr())
+        rc = lib.dcn_contrastive_loss_forward_save(*(args + (_lib.ptr(records), _lib.stream_ptr())))
     else:
-        rc = lib.dcn_contrastive_loss_forward(
-            _lib.ptr(desc_a), _lib.ptr(desc_b), P, HW, D, _lib.ptr(lists.idx_a), _lib.ptr(lists.idx_b),
-            ctypes.cast(lists._off_c, ctypes.c_void_p), _lib.ptr(lists.offsets_dev), ctypes.byref(cfg),
-            _lib.ptr(terms), _lib.ptr(sums), _lib.ptr(hard), _lib.ptr(loss), _lib.ptr(per_term), _lib.ptr(status),
-            _lib.ptr(ws), _lib.stream_ptr())
+        rc = lib.dcn_contrastive_loss_forward(*(args + (_lib.stream_ptr(),)))
     _lib.check(rc, "dcn_contrastive_loss_forward")
     return desc_a, desc_b, loss, terms, sums, hard, status, per_term
 
@@ -208,32 +223,23 @@ class _ContrastiveLossFn(torch.autograd.Function):
                 g2 = torch.empty((2, P, HW, D), dtype=torch.float32, device=hard.device)
             gl = grad_loss.reshape(1).to(torch.float32).contiguous()
             exact_bytes = int(lib.dcn_loss_exact_workspace_bytes(P, HW, D))
-            per_pair_max = max(lists.offsets_host[4 * p + 4] - lists.offsets_host[4 * p] for p in range(lists.num_pairs))
-            exact = (EXACT_BACKWARD if EXACT_BACKWARD is not None else exact_bytes <= EXACT_BACKWARD_MAX_BYTES) and \
-                per_pair_max < (1 << 22) and P <= 16383     # (maps zero-filled ahead of time, PREFILL_GRADIENTS, are simply overwritten)
-            if exact:
+            common = (P, HW, D) + _list_args(lists, cfg) + (_lib.ptr(hard), _lib.ptr(gl), _lib.ptr(ctx.records))
+            maps = (_lib.ptr(g2[0]), _lib.ptr(g2[1]), _lib.stream_ptr())
+            if _use_exact(exact_bytes, lists.max_pair_len, P):   # (maps zero-filled ahead of time, PREFILL_GRADIENTS, are simply overwritten)
                 ws = torch.empty(exact_bytes, dtype=torch.uint8, device=hard.device)
-                rc = lib.dcn_contrastive_loss_backward_saved_exact(
-                    P, HW, D, _lib.ptr(lists.idx_a), _lib.ptr(lists.idx_b), ctypes.cast(lists._off_c, ctypes.c_void_p),
-                    _lib.ptr(lists.offsets_dev), ctypes.byref(cfg), _lib.ptr(hard), _lib.ptr(gl), _lib.ptr(ctx.records),
-                    _lib.ptr(ws), _lib.ptr(g2[0]), _lib.ptr(g2[1]), _lib.stream_ptr())
+                rc = lib.dcn_contrastive_loss_backward_saved_exact(*(common + (_lib.ptr(ws),) + maps))
                 _lib.check(rc, "dcn_contrastive_loss_backward_saved_exact")
-                return g2[0], g2[1], None, None, None
-            rc = lib.dcn_contrastive_loss_backward_saved(
-                P, HW, D, _lib.ptr(lists.idx_a), _lib.ptr(lists.idx_b), ctypes.cast(lists._off_c, ctypes.c_void_p),
-                _lib.ptr(lists.offsets_dev), ctypes.byref(cfg), _lib.ptr(hard), _lib.ptr(gl), _lib.ptr(ctx.records), prefilled,
-                _lib.ptr(g2[0]), _lib.ptr(g2[1]), _lib.stream_ptr())
-            _lib.check(rc, "dcn_contrastive_loss_backward_saved")
+            else:
+                rc = lib.dcn_contrastive_loss_backward_saved(*(common + (prefilled,) + maps))
+                _lib.check(rc, "dcn_contrastive_loss_backward_saved")
             return g2[0], g2[1], None, None, None
         desc_a, desc_b, sums, hard = ctx.saved_tensors
         P, HW, D = desc_a.shape
         g2 = torch.empty((2,) + tuple(desc_a.shape), dtype=desc_a.dtype, device=desc_a.device)   # one allocation: the kernel side
         ga, gb = g2[0], g2[1]                                                                     # zero-fills both maps in one launch
         gl = grad_loss.reshape(1).to(torch.float32).contiguous()
-        rc = lib.dcn_contrastive_loss_backward(
-            _lib.ptr(desc_a), _lib.ptr(desc_b), P, HW, D, _lib.ptr(lists.idx_a), _lib.ptr(lists.idx_b),
-            ctypes.cast(lists._off_c, ctypes.c_void_p), _lib.ptr(lists.offsets_dev), ctypes.byref(cfg),
-            _lib.ptr(sums), _lib.ptr(hard), _lib.ptr(gl), None, _lib.ptr(ga), _lib.ptr(gb), _lib.stream_ptr())
+        rc = lib.dcn_contrastive_loss_backward(*((_lib.ptr(desc_a), _lib.ptr(desc_b), P, HW, D) + _list_args(lists, cfg) + (
+            _lib.ptr(sums), _lib.ptr(hard), _lib.ptr(gl), None, _lib.ptr(ga), _lib.ptr(gb), _lib.stream_ptr())))
         _lib.check(rc, "dcn_contrastive_loss_backward")
         return ga, gb, None, None, None
 
@@ -282,26 +288,15 @@ class _MixedLossFn(torch.autograd.Function):
     def forward(ctx, desc_a, desc_b, lists, table):
         lib = _lib.get()
         _lib.require_device(desc_a, desc_b, lists.idx_a, lists.idx_b, lists.offsets, lists.types)
-        if desc_a.dtype != torch.float32 or desc_b.dtype != torch.float32:
-            raise TypeError("dcn_hip loss kernels take float32 descriptor maps, got %s / %s (cast with .float(); the gradient "
-                            "then flows back through the cast)" % (desc_a.dtype, desc_b.dtype))
-        if desc_a.dim() != 3 or desc_b.shape != desc_a.shape or int(desc_a.shape[0]) != lists.num_pairs:
-            raise ValueError("descriptor maps %s / %s do not match %d pair lists" %
-                             (tuple(desc_a.shape), tuple(desc_b.shape), lists.num_pairs))
-        desc_a, desc_b = desc_a.contiguous(), desc_b.contiguous()
+        desc_a, desc_b = _check_maps(desc_a, desc_b, lists.num_pairs)
         P, HW, D = (int(x) for x in desc_a.shape)
         dev = desc_a.device
-        f32 = dict(dtype=torch.float32, device=dev)
-        terms = torch.empty(P, 5, **f32)
-        sums = torch.empty(P, 4, **f32)
-        hard = torch.empty(P, 4, dtype=torch.int32, device=dev)
-        loss = torch.empty(1, **f32)
+        terms, sums, hard, loss, status = _small_outputs(P, dev)
         num_valid = torch.empty(1, dtype=torch.int32, device=dev)
-        status = torch.empty(1, dtype=torch.int32, device=dev)
         ws = torch.empty(lib.dcn_loss_workspace_bytes(P, lists.max_list_len), dtype=torch.uint8, device=dev)
         records = None
         if (ctx.needs_input_grad[0] or ctx.needs_input_grad[1]) and lists.capacity > 0:
-            records = torch.empty(lib.dcn_loss_saved_floats(lists.capacity, D), **f32)
+            records = torch.empty(lib.dcn_loss_saved_floats(lists.capacity, D), dtype=torch.float32, device=dev)
         rc = lib.dcn_contrastive_loss_mixed_forward(
             _lib.ptr(desc_a), _lib.ptr(desc_b), P, HW, D, _lib.ptr(lists.idx_a), _lib.ptr(lists.idx_b), _lib.ptr(lists.offsets),
             _lib.ptr(lists.types), table, lists.max_list_len, lists.max_pair_len, lists.capacity, _lib.ptr(terms),
@@ -322,12 +317,10 @@ class _MixedLossFn(torch.autograd.Function):
         g2 = torch.empty((2, P, HW, D), dtype=torch.float32, device=hard.device)
         gl = grad_loss.reshape(1).to(torch.float32).contiguous()
         exact_bytes = int(lib.dcn_loss_exact_workspace_bytes(P, HW, D))
-        exact = (EXACT_BACKWARD if EXACT_BACKWARD is not None else exact_bytes <= EXACT_BACKWARD_MAX_BYTES) and \
-            lists.max_pair_len < (1 << 22)            # (the bound, not the lengths: those stay on the device)
         common = (P, HW, D, _lib.ptr(lists.idx_a), _lib.ptr(lists.idx_b), _lib.ptr(lists.offsets), _lib.ptr(lists.types), table,
                   lists.max_list_len, lists.max_pair_len, lists.capacity, _lib.ptr(hard), _lib.ptr(num_valid), _lib.ptr(gl),
                   _lib.ptr(ctx.records))
-        if exact:
+        if _use_exact(exact_bytes, lists.max_pair_len, P):   # (the bound, not the lengths: those stay on the device)
             ws = torch.empty(exact_bytes, dtype=torch.uint8, device=hard.device)
             rc = lib.dcn_contrastive_loss_mixed_backward_saved_exact(*(common + (_lib.ptr(ws), _lib.ptr(g2[0]), _lib.ptr(g2[1]),
                                                                                  _lib.stream_ptr())))
@@ -369,10 +362,8 @@ class _PerTermFn(torch.autograd.Function):
         ga = torch.empty_like(desc_a)
         gb = torch.empty_like(desc_b)
         gv = grad_vec.to(torch.float32).contiguous()
-        rc = lib.dcn_contrastive_loss_backward(
-            _lib.ptr(desc_a), _lib.ptr(desc_b), P, HW, D, _lib.ptr(lists.idx_a), _lib.ptr(lists.idx_b),
-            ctypes.cast(lists._off_c, ctypes.c_void_p), _lib.ptr(lists.offsets_dev), ctypes.byref(cfg),
-            None, None, None, _lib.ptr(gv), _lib.ptr(ga), _lib.ptr(gb), _lib.stream_ptr())
+        rc = lib.dcn_contrastive_loss_backward(*((_lib.ptr(desc_a), _lib.ptr(desc_b), P, HW, D) + _list_args(lists, cfg) + (
+            None, None, None, _lib.ptr(gv), _lib.ptr(ga), _lib.ptr(gb), _lib.stream_ptr())))
         _lib.check(rc, "dcn_contrastive_loss_backward(per-term)")
         return ga, gb, None, None
 

@@ -4,6 +4,7 @@ host (tests/hostemu).  CPU only; the same properties at training sizes on the gf
 
 Yardsticks: ``get_loss_batched`` (the one-type call the mixed call must reproduce bit for bit where both apply), the oracle
 (oracle/loss_oracle.py) and the reference's own goldens (tests/golden/loss_ref_*.npz)."""
+import ctypes
 import os
 
 import numpy as np
@@ -11,10 +12,12 @@ import pytest
 import torch
 
 import frames_common as fc
+import loss_mixed_common as mc
 from helpers import lists_from_golden, load_golden_loss, rel_err, use_emulation_library
+from loss_mixed_common import (ACROSS, DIFFERENT, MULTI, SYNTHETIC, WITHIN, descriptors, device_lists, make_lists, pcl_for,
+                               run_batched, run_mixed)
 
 GOLDEN_DIR = os.path.join(os.path.dirname(__file__), "golden")
-WITHIN, ACROSS, DIFFERENT, MULTI, SYNTHETIC = 0, 1, 2, 3, 4
 
 
 @pytest.fixture(scope="module", autouse=True)
@@ -27,60 +30,6 @@ def exact(monkeypatch):
     """DCN_LOSS_EXACT=1: the order-independent backward in both calls (the module reads the variable once, at import)."""
     from dcn_hip import loss as K
     monkeypatch.setattr(K, "EXACT_BACKWARD", True)
-
-
-def pcl_for(H, W, cfg=None):
-    from dense_correspondence.loss_functions.pixelwise_contrastive_loss import PixelwiseContrastiveLoss
-    from oracle import synth
-    return PixelwiseContrastiveLoss([H, W], cfg or synth.LOSS_CONFIG)
-
-
-def make_lists(code, HW, sizes, g):
-    """One 8-tuple: within-scene compositions fill all four lists (match, masked, background, blind), the across-scene and
-    different-object ones only the blind list."""
-    r = lambda n: torch.randint(0, HW, (n,), generator=g)
-    if code in (WITHIN, MULTI, SYNTHETIC):
-        pm, pk, pg, pb = sizes
-        return (r(pm), r(pm), r(pk), r(pk), r(pg), r(pg), r(pb) if pb else None, r(pb) if pb else None)
-    return (None, None, None, None, None, None, r(sizes[3]), r(sizes[3]))
-
-
-def device_lists(pairs, types, tail=37, max_list_len=None, max_pair_len=None):
-    """The lists of ``pairs`` as a device-built batch would hold them: concatenated, a -1 tail up to the capacity, device
-    offsets and types, and generous bounds (several workgroups past the longest list)."""
-    from dcn_hip import loss as K
-    pl = K.PairLists.from_lists(pairs, "cpu")
-    fill = torch.full((tail,), -1, dtype=torch.int64)
-    ia = torch.cat([pl.idx_a[:pl.total], fill])
-    ib = torch.cat([pl.idx_b[:pl.total], fill])
-    per_pair = max(pl.offsets_host[4 * p + 4] - pl.offsets_host[4 * p] for p in range(pl.num_pairs))
-    return K.DeviceLists(ia, ib, pl.offsets_dev, torch.tensor(types, dtype=torch.int32),
-                         2 * pl.max_len + 1500 if max_list_len is None else max_list_len,
-                         per_pair + 1500 if max_pair_len is None else max_pair_len)
-
-
-def descriptors(B, HW, D, seed):
-    g = torch.Generator().manual_seed(seed)
-    mk = lambda: ((torch.rand(B, HW, D, generator=g) * 2 - 1) * 0.6 / D ** 0.5).requires_grad_(True)
-    return mk(), mk()
-
-
-def run_mixed(pcl, A, B, lists):
-    from dense_correspondence.loss_functions import loss_composer
-    A = A.detach().clone().requires_grad_(True)
-    B = B.detach().clone().requires_grad_(True)
-    loss, terms, hard, nv = loss_composer.get_loss_mixed(pcl, A, B, lists)
-    loss.backward()
-    return dict(loss=loss.detach(), terms=terms, hard=hard, num_valid=int(nv), gA=A.grad, gB=B.grad, status=int(pcl.last_status))
-
-
-def run_batched(pcl, code, A, B, pairs):
-    from dense_correspondence.loss_functions import loss_composer
-    A = A.detach().clone().requires_grad_(True)
-    B = B.detach().clone().requires_grad_(True)
-    loss, terms, hard = loss_composer.get_loss_batched(pcl, code, A, B, pairs)
-    loss.backward()
-    return dict(loss=loss.detach(), terms=terms, hard=hard, gA=A.grad, gB=B.grad, status=int(pcl.last_status))
 
 
 SIZES = [(50, 1100, 70, 33), (1, 3, 2, 5), (2049, 5, 1025, 600)]   # crosses the pairs-per-workgroup chunk boundaries
@@ -488,3 +437,167 @@ def test_draw_training_batch_default_is_unchanged():
             assert torch.equal(getattr(sb, k), getattr(ref, k)), k
         assert sb[:12] == sb[:12] and len(sb) == 14 and sb._fields[:12] == (
             "input_a", "input_b", "idx_a", "idx_b", "offsets", "empty", "type", "status", "seeds", "aug_params", "mask_a", "mask_b")
+
+
+# ------------------------------------------------------------------------------------------------ 7. every arm at every site
+# (rtol / atol of the terms and the gradient bound: test_mixed_types_compose_each_pair_by_its_own_type's, against the same oracle)
+@pytest.mark.parametrize("site,D", mc.ONE_TYPE_CASES)
+def test_one_type_launch_sites_at_the_remaining_descriptor_widths(site, D):
+    mc.check_one_type_dispatch(site, D, "cpu", rtol=1e-5, atol=1e-9, grad_tol=1e-5)
+
+
+@pytest.mark.parametrize("site,D", mc.MIXED_CASES)
+def test_mixed_launch_sites_at_the_remaining_descriptor_widths(site, D):
+    mc.check_mixed_dispatch(site, D, "cpu", rtol=1e-5, atol=1e-9, grad_tol=1e-5)
+
+
+# ------------------------------------------------------------------------------------------------ 8. refusal codes
+OK, E_INVALID, E_UNSUPPORTED = 0, -1, -3                  # include/dcn_hip.h
+
+
+class _Refusals(object):
+    """Valid arguments of the six contrastive entry points at P = 1, HW = 16, D = 3 (or ``P`` pairs with empty lists), as
+    name -> value in the order of the C signature; ``call(entry, name=value, ...)`` replaces some and returns the code."""
+
+    def __init__(self, P=1, offsets=(0, 5, 9, 12, 14)):
+        from dcn_hip import _lib as L
+        from dcn_hip import loss as K
+        self.L, self.lib = L, L.get()
+        HW, D = 16, 3
+        off = list(offsets) if P == 1 else [0] * (4 * P + 1)
+        total = off[-1]
+        self.keep = k = dict(
+            desc=torch.zeros(2, P, HW, D), idx=torch.zeros(2, max(total, 1), dtype=torch.int64),
+            off_dev=torch.tensor(off, dtype=torch.int64), types=torch.zeros(P, dtype=torch.int32),
+            terms=torch.zeros(P, 5), sums=torch.zeros(P, 4), hard=torch.zeros(P, 4, dtype=torch.int32), loss=torch.zeros(1),
+            status=torch.zeros(1, dtype=torch.int32), num_valid=torch.ones(1, dtype=torch.int32), gl=torch.ones(1),
+            ws=torch.zeros(int(self.lib.dcn_loss_workspace_bytes(P, 5)), dtype=torch.uint8),
+            records=torch.zeros(max(total, 1) * (D + 1)), grads=torch.ones(2, P, HW, D),
+            xws=torch.full((int(self.lib.dcn_loss_exact_workspace_bytes(P, HW, D)),), 255, dtype=torch.uint8))
+        self.off_c = (ctypes.c_int64 * len(off))(*off)
+        self.cfg = K.make_config([0, .5, .5, .5], 4)
+        self.table = K.config_table([self.cfg] * K.NUM_TYPES)
+        p = L.ptr
+        lists = [("idx_a", p(k["idx"][0])), ("idx_b", p(k["idx"][1]))]
+        host = lists + [("offsets_host", ctypes.cast(self.off_c, ctypes.c_void_p)), ("offsets_dev", p(k["off_dev"])),
+                        ("cfg", ctypes.byref(self.cfg))]
+        mixed = lists + [("offsets_dev", p(k["off_dev"])), ("types_dev", p(k["types"])), ("cfgs", self.table),
+                         ("max_list_len", 5), ("max_pair_len", 14), ("capacity", total)]
+        shape = [("num_pairs", P), ("hw", HW), ("d", D)]
+        descs = [("desc_a", p(k["desc"][0])), ("desc_b", p(k["desc"][1]))]
+        outs = [("terms", p(k["terms"])), ("sums", p(k["sums"])), ("hard_neg", p(k["hard"])), ("loss", p(k["loss"]))]
+        grads = [("grad_a", p(k["grads"][0])), ("grad_b", p(k["grads"][1])), ("stream", None)]
+        back = [("hard_neg", p(k["hard"])), ("grad_loss", p(k["gl"])), ("pair_records", p(k["records"]))]
+        mback = [("hard_neg", p(k["hard"])), ("num_valid", p(k["num_valid"])), ("grad_loss", p(k["gl"])),
+                 ("pair_records", p(k["records"]))]
+        fwd = descs + shape + host + outs + [("per_term", None), ("status", p(k["status"])), ("workspace", p(k["ws"]))]
+        self.args = {
+            "forward": fwd + [("stream", None)],
+            "forward_save": fwd + [("pair_records", p(k["records"])), ("stream", None)],
+            "backward": descs + shape + host + [("sums", p(k["sums"])), ("hard_neg", p(k["hard"])), ("grad_loss", p(k["gl"])),
+                                                ("pair_grad", None)] + grads,
+            "backward_saved": shape + host + back + [("prefilled", 0)] + grads,
+            "backward_saved_exact": shape + host + back + [("workspace", p(k["xws"]))] + grads,
+            "mixed_forward": descs + shape + mixed + outs + [("num_valid", p(k["num_valid"])), ("status", p(k["status"])),
+                                                             ("workspace", p(k["ws"])), ("pair_records", p(k["records"])),
+                                                             ("stream", None)],
+            "mixed_backward_saved": shape + mixed + mback + [("prefilled", 0)] + grads,
+            "mixed_backward_saved_exact": shape + mixed + mback + [("workspace", p(k["xws"]))] + grads,
+        }
+
+    def call(self, entry, **replace):
+        names = [n for n, _ in self.args[entry]]
+        assert set(replace) <= set(names), (entry, sorted(set(replace) - set(names)))
+        fn = getattr(self.lib, "dcn_contrastive_loss_" + entry)
+        assert len(names) == len(self.L.SYMBOLS["dcn_contrastive_loss_" + entry][1])
+        return fn(*[replace.get(n, v) for n, v in self.args[entry]])
+
+
+REQUIRED = {   # the pointers each entry point refuses as null whatever the lists hold
+    "forward": ["desc_a", "desc_b", "offsets_host", "offsets_dev", "cfg", "terms", "sums", "hard_neg", "loss", "status", "workspace"],
+    "forward_save": ["pair_records", "offsets_host", "desc_a", "workspace"],
+    "backward": ["desc_a", "desc_b", "offsets_host", "offsets_dev", "cfg", "grad_a", "grad_b", "hard_neg", "grad_loss"],
+    "backward_saved": ["offsets_host", "offsets_dev", "cfg", "hard_neg", "grad_loss", "pair_records", "grad_a", "grad_b"],
+    "backward_saved_exact": ["offsets_host", "offsets_dev", "cfg", "hard_neg", "grad_loss", "pair_records", "workspace", "grad_a",
+                             "grad_b"],
+    "mixed_forward": ["offsets_dev", "types_dev", "cfgs", "idx_a", "idx_b", "desc_a", "desc_b", "terms", "sums", "hard_neg",
+                      "loss", "num_valid", "status", "workspace"],
+    "mixed_backward_saved": ["offsets_dev", "types_dev", "cfgs", "idx_a", "idx_b", "hard_neg", "num_valid", "grad_loss", "grad_a",
+                             "grad_b"],
+    "mixed_backward_saved_exact": ["offsets_dev", "types_dev", "cfgs", "idx_a", "idx_b", "hard_neg", "num_valid", "grad_loss",
+                                   "workspace", "grad_a", "grad_b"],
+}
+
+
+@pytest.mark.parametrize("entry", sorted(REQUIRED))
+def test_refusal_null_pointer_or_no_pairs(entry):
+    r = _Refusals()
+    for name in REQUIRED[entry]:
+        assert r.call(entry, **{name: None}) == E_INVALID, name
+    for bad in (dict(num_pairs=0), dict(hw=0), dict(d=0)):
+        assert r.call(entry, **bad) == E_INVALID, bad
+    if entry.startswith("mixed"):
+        for bad in (dict(max_list_len=-1), dict(max_pair_len=-1), dict(capacity=-1)):
+            assert r.call(entry, **bad) == E_INVALID, bad
+    assert not r.keep["terms"].any() and bool((r.keep["grads"] == 1).all()) and bool((r.keep["xws"] == 255).all())   # nothing ran
+
+
+def test_refusal_offsets_and_lists_of_the_forward():
+    r = _Refusals()
+    down = (ctypes.c_int64 * 5)(0, 5, 4, 12, 14)
+    for entry in ("forward", "forward_save"):
+        assert r.call(entry, offsets_host=ctypes.cast(down, ctypes.c_void_p)) == E_INVALID
+        assert r.call(entry, idx_a=None) == E_INVALID and r.call(entry, idx_b=None) == E_INVALID    # 14 entries, no lists
+    e = _Refusals(offsets=(0, 0, 0, 0, 0))
+    assert e.call("forward", idx_a=None, idx_b=None) == OK                                           # nothing to read
+
+
+def test_refusal_too_many_pairs_is_unsupported_after_invalid():
+    P = 16384                                                     # grid.y = 4 P of the launches: past 65535
+    r = _Refusals(P=P)
+    for entry in ("backward_saved_exact", "mixed_forward", "mixed_backward_saved", "mixed_backward_saved_exact"):
+        assert r.call(entry) == E_UNSUPPORTED, entry
+    # DCN_E_INVALID first on the one-type entry; on the mixed ones mixed_args (with the pair count) before the entry's own
+    # null checks
+    assert r.call("backward_saved_exact", workspace=None) == E_INVALID
+    assert r.call("backward_saved_exact", num_pairs=0) == E_INVALID
+    assert r.call("mixed_forward", terms=None) == E_UNSUPPORTED
+    assert r.call("mixed_backward_saved", grad_a=None) == E_UNSUPPORTED
+    assert r.call("mixed_backward_saved_exact", workspace=None) == E_UNSUPPORTED
+    assert r.call("mixed_forward", types_dev=None) == E_INVALID
+    assert bool((r.keep["grads"] == 1).all())
+
+
+def test_refusal_pair_of_two_to_the_22_entries():
+    """The one-type entry reads the host offsets, the mixed one the host bound (clipped to the capacity): both return before
+    anything on the device is read, so the lists themselves need not exist."""
+    big = 1 << 22
+    r = _Refusals()
+    claimed = (ctypes.c_int64 * 5)(0, big, big, big, big)
+    assert r.call("backward_saved_exact", offsets_host=ctypes.cast(claimed, ctypes.c_void_p)) == E_UNSUPPORTED
+    assert r.call("backward_saved_exact", offsets_host=ctypes.cast(claimed, ctypes.c_void_p), grad_b=None) == E_INVALID
+    assert r.call("mixed_backward_saved_exact", max_pair_len=big, capacity=big) == E_UNSUPPORTED
+    assert r.call("mixed_backward_saved_exact", max_pair_len=big, capacity=big, workspace=None) == E_INVALID
+    assert bool((r.keep["xws"] == 255).all()) and bool((r.keep["grads"] == 1).all())
+
+
+def test_refusal_null_lists_or_records_after_the_fill():
+    """Non-empty lists without idx_a / idx_b (one-type) or without pair_records (mixed): DCN_E_INVALID, after the gradient maps
+    / the workspace have been zero-filled; with empty lists the same calls return DCN_OK after the fill."""
+    for entry, missing in (("backward_saved", dict(idx_a=None)), ("backward_saved", dict(idx_b=None)),
+                           ("mixed_backward_saved", dict(pair_records=None))):
+        r = _Refusals()
+        assert r.call(entry, **missing) == E_INVALID, (entry, missing)
+        assert not r.keep["grads"].any()
+        r = _Refusals()
+        assert r.call(entry, prefilled=1, **missing) == E_INVALID
+        assert bool((r.keep["grads"] == 1).all())                 # (prefilled: the caller's fill is kept)
+    for entry, missing in (("backward_saved_exact", dict(idx_a=None)), ("mixed_backward_saved_exact", dict(pair_records=None))):
+        r = _Refusals()
+        assert r.call(entry, **missing) == E_INVALID, (entry, missing)
+        assert not r.keep["xws"].any() and bool((r.keep["grads"] == 1).all())
+    e = _Refusals(offsets=(0, 0, 0, 0, 0))
+    assert e.call("backward_saved", idx_a=None, idx_b=None) == OK and not e.keep["grads"].any()
+    e = _Refusals()
+    assert e.call("mixed_backward_saved", max_list_len=0, pair_records=None) == OK and not e.keep["grads"].any()
+    assert _Refusals().call("backward_saved", pair_records=None) == E_INVALID                          # required, lists or not

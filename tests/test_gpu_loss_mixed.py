@@ -6,6 +6,7 @@ import numpy as np
 import pytest
 import torch
 
+import loss_mixed_common as mc
 from helpers import rel_err, use_gfx950_library
 
 pytestmark = pytest.mark.gpu
@@ -170,6 +171,18 @@ def test_exact_backward_is_bit_reproducible_with_shuffled_lists(exact):
     assert torch.equal(first["loss"], again["loss"]) and torch.equal(first["hard"], other["hard"])
     assert torch.equal(first["gA"], other["gA"]) and torch.equal(first["gB"], other["gB"])
     assert float(first["gA"].abs().max()) > 0
+
+
+# ------------------------------------------------------------------------------------------------ every arm at every site
+# (the cases of tests/test_emu_loss_mixed.py on the device, at this file's tolerance)
+@pytest.mark.parametrize("site,D", mc.ONE_TYPE_CASES)
+def test_one_type_launch_sites_at_the_remaining_descriptor_widths(site, D):
+    mc.check_one_type_dispatch(site, D, "cuda", rtol=TOL, atol=0, grad_tol=TOL)
+
+
+@pytest.mark.parametrize("site,D", mc.MIXED_CASES)
+def test_mixed_launch_sites_at_the_remaining_descriptor_widths(site, D):
+    mc.check_mixed_dispatch(site, D, "cuda", rtol=TOL, atol=0, grad_tol=TOL)
 
 
 # ------------------------------------------------------------------------------------------------ frame store -> optimizer step
