@@ -928,6 +928,36 @@ int dcn_match_statistics_pairs(int p, int h, int w, int d, const float* res_a, c
                                int max_pair_rows, double* columns, uint8_t* is_valid, int32_t* pred_uv, int32_t* closer,
                                int32_t* row_pair, int32_t* mask_pixels, int32_t* status, void* workspace, void* stream);
 
+/* =====================================================================================================
+ * 12. Descriptor statistics of a dataset -- replaces, for device-resident descriptor images, the per-image half and the
+ *     running update of DenseCorrespondenceEvaluation.compute_descriptor_statistics_on_dataset
+ *     (dense_correspondence/evaluation/evaluation.py:2157-2304), whose result descriptor_statistics.yaml colours descriptor
+ *     images (DenseCorrespondenceNetwork.descriptor_image_stats).
+ *
+ * 12a. Per image (compute_descriptor_statistics, :2177-2219): res float [n][hw][d] descriptor images (channel last, as
+ *     forward_image_tensors returns them); mask uint8 [n][hw] (non-zero: on the object).  ONE read of res and of mask gives
+ *       per_image float [n][2][3][d]: (entire image, mask) x (min, max, mean) per channel; mask_pixels int32 [n].
+ *     Sums are accumulated in float64 and divided by the float64 count; the mean is rounded to fp32 once.  Workgroups per
+ *     image grow with h * w; their partials are folded in a fixed order by a second launch (no floating-point atomics): the
+ *     result is the same bit for bit from run to run.  NaN as in torch: a NaN anywhere in a channel makes that channel's min,
+ *     max and mean NaN -- for the mask rows only a NaN under the mask.  An image whose mask is empty has mask_pixels 0 and NaN
+ *     in its mask rows (the reference returns None, None there, :2203-2204).
+ *     1 <= n <= 65535, 1 <= d <= 64, h * w < 2^31.  workspace: dcn_descriptor_statistics_workspace(n, h, w, d) bytes.
+ *
+ * 12b. Over the images (update_stats and the final scaling, :2237-2292): per_image [n][2][3][d] and mask_pixels [n] as 12a
+ *     writes them.  An image with mask_pixels == 0 is skipped for BOTH sets (:2280-2282); min and max over the images used
+ *     (torch.min / torch.max: NaN if either is); mean: the fp32 sum of the used images' fp32 means, added in image order, times
+ *     (float)(1.0 / num_images) -- num_images, not the number used: the reference's divisor (:2290).
+ *       stats float [2][3][d]; used int32 [1].  No image used: stats is NaN.
+ *     One workgroup.  n >= 1, num_images >= 1, 1 <= d <= 64.
+ *     No host synchronisation in either.
+ * ===================================================================================================== */
+size_t dcn_descriptor_statistics_workspace(int n, int h, int w, int d);
+int dcn_descriptor_statistics(int n, int h, int w, int d, const float* res, const uint8_t* mask, float* per_image,
+                              int32_t* mask_pixels, void* workspace, void* stream);
+int dcn_descriptor_statistics_combine(int n, int d, const float* per_image, const int32_t* mask_pixels, int num_images,
+                                      float* stats, int32_t* used, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -8,9 +8,14 @@ of a ``frames.FrameStore``.
 frames, normalizes them, runs the network in eval mode, finds and subsamples the ground-truth matches and computes every
 column of the reference's table for all pairs, without reading anything back; ``evaluate_network`` composes the two and
 copies the table to the host once.
+
+``compute_descriptor_statistics_on_dataset`` (csrc/descstats_kernels.hip) is the first quantitative part of the reference's
+``run_evaluation_on_network`` (evaluation.py:2157-2304): the per-channel min, max and mean of the descriptors over random
+frames of the store, for the whole image and for the object mask, written to ``descriptor_statistics.yaml``.
 """
 import collections
 import ctypes
+import os
 
 import numpy as np
 import torch
@@ -162,6 +167,27 @@ def _below(rng, n):
     return int(rng.integers(n)) if hasattr(rng, "integers") else int(rng.randint(n))
 
 
+def _lots(store):
+    lots = len(store.multi_scenes_host) + len(store.object_scenes_host)
+    if lots == 0:
+        raise ValueError("I don't think you have any scenes?")
+    return lots
+
+
+def _random_scene(store, rng, lots):
+    """``get_random_scene_name`` (spartan_dataset_masked.py:521-541) on the store's host tables: two or three draws;
+    ``lots`` = _lots(store)"""
+    multi, per_object = store.multi_scenes_host, store.object_scenes_host
+    k = _below(rng, lots)
+    if k < len(multi):
+        return multi[_below(rng, len(multi))]
+    o = _below(rng, len(per_object))
+    scenes = per_object[o]
+    if not scenes:
+        raise ValueError("object %s has no scene in this store" % (store.object_ids[o],))
+    return scenes[_below(rng, len(scenes))]
+
+
 def choose_pairs(store, num_image_pairs, host_rng=None, threshold=0.05, max_num_attempts=100):
     """``num_image_pairs`` times the reference's per-pair rule, on the host: a scene by ``get_random_scene_name``
     (spartan_dataset_masked.py:521-541: one lot per multi-object scene and per object; then uniform over the multi-object
@@ -177,22 +203,11 @@ def choose_pairs(store, num_image_pairs, host_rng=None, threshold=0.05, max_num_
     -> int64 array [n, 3] of (scene, frame a, frame b), frames as store indices; n <= num_image_pairs."""
     rng = host_rng if host_rng is not None else np.random
     first = store.scene_first_frame_host
-    multi, per_object = store.multi_scenes_host, store.object_scenes_host
-    lots = len(multi) + len(per_object)
-    if lots == 0:
-        raise ValueError("I don't think you have any scenes?")
+    lots = _lots(store)
     t = store.translations_host
     out = []
     for _ in range(int(num_image_pairs)):
-        k = _below(rng, lots)
-        if k < len(multi):
-            s = multi[_below(rng, len(multi))]
-        else:
-            o = _below(rng, len(per_object))
-            scenes = per_object[o]
-            if not scenes:
-                raise ValueError("object %s has no scene in this store" % (store.object_ids[o],))
-            s = scenes[_below(rng, len(scenes))]
+        s = _random_scene(store, rng, lots)
         lo, cnt = first[s], first[s + 1] - first[s]
         a = lo + _below(rng, cnt)
         for _attempt in range(int(max_num_attempts)):
@@ -301,3 +316,163 @@ def evaluate_network(dcn, store, num_image_pairs=25, num_matches_per_image_pair=
     except ImportError:
         df = None
     return table, df
+
+
+def descriptor_statistics(res, mask):
+    """``compute_descriptor_statistics`` (evaluation.py:2177-2219) for n descriptor images in ONE pass over ``res`` and ``mask``.
+
+    res: float32 [n, H, W, D] descriptor images, channel last, as ``forward_image_tensors`` returns them (D = 1 .. 64); mask:
+    uint8 or bool [n, H, W] (non-zero = on the object).
+    -> (per_image float32 [n, 2, 3, D]: axis 1 entire image, mask; axis 2 min, max, mean; mask_pixels int32 [n]).  Sums in
+    float64, the mean rounded to float32 once; bit-identical from run to run; NaN as in torch (a NaN in a channel makes its
+    min, max and mean NaN; for the mask rows only a NaN under the mask); an empty mask gives mask_pixels 0 and NaN mask rows.
+    No host synchronization."""
+    lib = _lib.get()
+    if not torch.is_tensor(res) or not torch.is_tensor(mask):
+        raise ValueError("res and mask must be tensors")
+    if res.dim() != 4:
+        raise ValueError("res must be [n, H, W, D], got %s" % (tuple(res.shape),))
+    if res.dtype != torch.float32:
+        raise ValueError("res must be float32, got %s" % res.dtype)
+    n, h, w, d = (int(x) for x in res.shape)
+    if d < 1 or d > 64:
+        raise ValueError("descriptor dimension must be 1 .. 64, got %d" % d)
+    if n < 1 or n > 65535 or h < 1 or w < 1 or h * w >= 2 ** 31:
+        raise ValueError("res must hold 1 .. 65535 images of 1 <= H * W < 2^31 pixels, got %s" % (tuple(res.shape),))
+    if mask.dtype not in (torch.uint8, torch.bool):
+        raise ValueError("mask must be uint8 (or bool), got %s" % mask.dtype)
+    m = _mask(mask, n, h, w, "mask")
+    r = res.contiguous()
+    try:
+        _lib.require_device(r, m)
+    except RuntimeError as e:
+        raise ValueError(str(e))
+    if r.device != m.device:
+        raise ValueError("res and mask must be on one device, got %s and %s" % (r.device, m.device))
+    dev = r.device
+    per_image = torch.empty((n, 2, 3, d), dtype=torch.float32, device=dev)
+    mask_pixels = torch.empty(n, dtype=torch.int32, device=dev)
+    ws = torch.empty(max(1, int(lib.dcn_descriptor_statistics_workspace(n, h, w, d))), dtype=torch.uint8, device=dev)
+    p = _lib.ptr
+    rc = lib.dcn_descriptor_statistics(n, h, w, d, p(r), p(m), p(per_image), p(mask_pixels), p(ws), _lib.stream_ptr())
+    _lib.check(rc, "dcn_descriptor_statistics")
+    return per_image, mask_pixels
+
+
+def combine_descriptor_statistics(per_image, mask_pixels, num_images=None):
+    """The reference's ``update_stats`` loop and final scaling (evaluation.py:2237-2292) over ``descriptor_statistics``'
+    outputs (per_image float32 [N, 2, 3, D], mask_pixels int32 [N]) in one launch: images with an empty mask are skipped for
+    both sets of statistics, min / max over the images used, mean = the float32 sum of their means in image order times
+    float32(1.0 / num_images) -- ``num_images`` (default N), not the number used, as in the reference.
+    -> (stats float32 [2, 3, D], used int32 [1]); ``stats`` is NaN when no image was used.  No host synchronization."""
+    lib = _lib.get()
+    if not torch.is_tensor(per_image) or per_image.dim() != 4 or tuple(per_image.shape[1:3]) != (2, 3) \
+            or per_image.dtype != torch.float32:
+        raise ValueError("per_image must be float32 [N, 2, 3, D]")
+    N, d = int(per_image.shape[0]), int(per_image.shape[3])
+    if N < 1 or d < 1 or d > 64:
+        raise ValueError("per_image must hold N >= 1 images of 1 .. 64 channels, got %s" % (tuple(per_image.shape),))
+    if not torch.is_tensor(mask_pixels) or mask_pixels.dtype != torch.int32 or tuple(mask_pixels.shape) != (N,):
+        raise ValueError("mask_pixels must be int32 [%d]" % N)
+    num = N if num_images is None else int(num_images)
+    if num < 1:
+        raise ValueError("num_images must be >= 1, got %d" % num)
+    pi, mp = per_image.contiguous(), mask_pixels.contiguous()
+    try:
+        _lib.require_device(pi, mp)
+    except RuntimeError as e:
+        raise ValueError(str(e))
+    dev = pi.device
+    stats = torch.empty((2, 3, d), dtype=torch.float32, device=dev)
+    used = torch.empty(1, dtype=torch.int32, device=dev)
+    p = _lib.ptr
+    rc = lib.dcn_descriptor_statistics_combine(N, d, p(pi), p(mp), num, p(stats), p(used), _lib.stream_ptr())
+    _lib.check(rc, "dcn_descriptor_statistics_combine")
+    return stats, used
+
+
+def choose_frames(store, num_images, host_rng=None):
+    """``num_images`` times the rule of ``get_random_rgbd_mask_pose`` (spartan_dataset_masked.py:410-421), on the host: a scene
+    by ``get_random_scene_name`` (as ``choose_pairs``), then a frame uniform over that scene's frames.  As in ``choose_pairs``
+    the rule is replayed, not the reference's random stream (it draws the scene and the image twice, :418-419).
+    ``host_rng``: a numpy RandomState / Generator (default ``np.random``).
+    -> int64 array [num_images, 2] of (scene, frame), frames as store indices."""
+    rng = host_rng if host_rng is not None else np.random
+    first = store.scene_first_frame_host
+    lots = _lots(store)
+    out = []
+    for _ in range(int(num_images)):
+        s = _random_scene(store, rng, lots)
+        out.append((s, first[s] + _below(rng, first[s + 1] - first[s])))
+    return np.asarray(out, dtype=np.int64).reshape(-1, 2)
+
+
+STAT_SETS, STAT_FIELDS = ("entire_image", "mask_image"), ("min", "max", "mean")
+
+
+def compute_descriptor_statistics_on_dataset(dcn, store, num_images=100, save_to_file=True, filename=None, host_rng=None,
+                                             batch_images=16):
+    """``DenseCorrespondenceEvaluation.compute_descriptor_statistics_on_dataset`` (evaluation.py:2157-2304) on a frame store:
+    1. choose_frames, 2. ONE ``dcn_gather_frames`` of their images and masks, 3. ToTensor + Normalize by the augmentation kernel
+    with every augmentation switched off (the dataset's mean and standard deviation, as ``evaluate_frame_pairs``), 4. ``dcn.forward_image_tensors`` in eval mode,
+    ``batch_images`` images at a time, 5. descriptor_statistics per batch into slices of one [num_images, 2, 3, D] tensor,
+    6. one combine_descriptor_statistics launch, 7. ONE copy to the host.
+    -> the reference's dict {'entire_image': {'min': [...], 'max': [...], 'mean': [...]}, 'mask_image': {...}} of lists of
+    Python floats, written with ``utils.saveToYaml`` when ``save_to_file`` -- to ``filename``, by default
+    ``<dcn's network params folder>/descriptor_statistics.yaml``, the file ``dcn.descriptor_image_stats`` reads.  ValueError
+    when every chosen frame's mask was empty (the reference fails on ``None.tolist()``).  ``dcn.training`` is left as found."""
+    n = int(num_images)
+    step = int(batch_images)
+    if n < 1 or n > 65534:
+        raise ValueError("num_images must be 1 .. 65534, got %d" % n)
+    if step < 1:
+        raise ValueError("batch_images must be >= 1")
+    if save_to_file and filename is None:                   # (before any work: a network without the folder cannot save)
+        import dense_correspondence_manipulation.utils.utils as utils
+        filename = os.path.join(utils.convert_to_absolute_path(dcn.path_to_network_params_folder),
+                                "descriptor_statistics.yaml")
+    chosen = choose_frames(store, n, host_rng)
+    lib = _lib.get()
+    dev = store.device
+    h, w = store.h, store.w
+    # the gather copies pairs of frames: frames [0, P) in slot 0 and [P, n) in slot 1 (an odd n repeats the last frame), so
+    # that the [2, P] planes, flattened, are the n frames in order
+    P = (n + 1) // 2
+    fr = np.concatenate([chosen[:, 1], chosen[-1:, 1]])[:2 * P].reshape(2, P).T
+    frames = torch.from_numpy(np.concatenate([fr, np.full((P, 2), -1, np.int64)], axis=1).astype(np.int32)).to(dev)
+    rgb = torch.empty((2, P, h, w, 3), dtype=torch.uint8, device=dev)
+    mask = torch.empty((2, P, h, w), dtype=torch.uint8, device=dev)
+    bad_frame = torch.zeros(1, dtype=torch.int32, device=dev)
+    p = _lib.ptr
+    rc = lib.dcn_gather_frames(P, 2, ctypes.byref(store.desc), p(frames), None, p(rgb), None, p(mask), None, p(bad_frame),
+                               _lib.stream_ptr())
+    _lib.check(rc, "dcn_gather_frames")
+    rgb, mask = rgb.view(2 * P, h, w, 3), mask.view(2 * P, h, w)
+    per_image = mask_pixels = None
+    params = torch.zeros((min(step, n), _aug.PARAM_WORDS), dtype=torch.int32, device=dev)   # (every augmentation off)
+    was_training = dcn.training
+    dcn.eval()
+    try:
+        for lo in range(0, n, step):
+            k = min(step, n - lo)
+            x = _aug.augment_images(rgb[lo:lo + k], mask[lo:lo + k], params[:k], want_mask=False)
+            res = dcn.forward_image_tensors(x["input_a"])
+            if per_image is None:
+                per_image = torch.empty((n, 2, 3, int(res.shape[3])), dtype=torch.float32, device=dev)
+                mask_pixels = torch.empty(n, dtype=torch.int32, device=dev)
+            per_image[lo:lo + k], mask_pixels[lo:lo + k] = descriptor_statistics(res, mask[lo:lo + k])
+    finally:
+        dcn.train(was_training)
+    stats, used = combine_descriptor_statistics(per_image, mask_pixels, n)
+    # one transfer: the statistics, the number of images used and the gather's status word in one float64 block
+    block = torch.cat([stats.double().view(-1), used.double(), bad_frame.double()]).cpu().numpy()
+    if int(block[-1]) != 0:
+        raise RuntimeError("dcn_hip: the frame gather rejected a frame index (status %d)" % int(block[-1]))
+    if int(block[-2]) == 0:
+        raise ValueError("every one of the %d chosen frames has an empty mask: no descriptor statistics" % n)
+    table = block[:-2].reshape(2, 3, -1)
+    out = {s: {f: [float(v) for v in table[i, j]] for j, f in enumerate(STAT_FIELDS)} for i, s in enumerate(STAT_SETS)}
+    if save_to_file:
+        import dense_correspondence_manipulation.utils.utils as utils
+        utils.saveToYaml(out, filename)
+    return out
