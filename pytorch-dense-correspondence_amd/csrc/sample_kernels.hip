@@ -479,15 +479,19 @@ struct Workspace {
     float *u2, *v2;
 };
 
+// The stride of the compacted lists: a source has hw elements (a mask) or `attempts` (the candidate flags)
+inline int64_t list_stride(int64_t hw, int64_t attempts) { return hw > attempts ? hw : attempts; }
+
+inline int segs_of(int64_t hw, int64_t attempts) { return (int)dcn::ceil_div64(list_stride(hw, attempts), kSeg); }
+
 // stride: match slots per pair (within: attempts; complete: the external lists' total)
 inline size_t carve(Workspace* w, char* base, int n, int64_t hw, int64_t attempts, int64_t stride) {
     stride = stride > 0 ? stride : 1;
-    const int segs = (int)dcn::ceil_div64(hw > attempts ? hw : attempts, kSeg);
     size_t o = 0;
     auto take = [&](size_t bytes) { const size_t at = o; o += align256(bytes); return base ? base + at : nullptr; };
     char* p;
-    p = take((size_t)NSRC * n * (hw > attempts ? hw : attempts) * 4); if (w) w->lists = (int32_t*)p;
-    p = take((size_t)NSRC * n * segs * 4);             if (w) w->seg = (int32_t*)p;
+    p = take((size_t)NSRC * n * list_stride(hw, attempts) * 4); if (w) w->lists = (int32_t*)p;
+    p = take((size_t)NSRC * n * segs_of(hw, attempts) * 4); if (w) w->seg = (int32_t*)p;
     p = take((size_t)NSRC * n * 8);                    if (w) w->counts = (int64_t*)p;
     p = take((size_t)n * 8);                           if (w) w->mcount = (int64_t*)p;
     p = take((size_t)n * attempts * 4);                if (w) w->pix = (int32_t*)p;
@@ -499,8 +503,6 @@ inline size_t carve(Workspace* w, char* base, int n, int64_t hw, int64_t attempt
     p = take((size_t)n * hw);                          if (w) w->matched = (uint8_t*)p;
     return o;
 }
-
-inline int segs_of(int64_t hw, int64_t attempts) { return (int)dcn::ceil_div64(hw > attempts ? hw : attempts, kSeg); }
 
 inline void compact(Common c, uint32_t src_mask, hipStream_t st) {
     c.src_mask = src_mask;
@@ -520,6 +522,24 @@ inline bool aligned16(const void* p) { return ((uintptr_t)p & 15u) == 0; }
 
 inline bool shape_ok(int n, int h, int w) {
     return n >= 1 && n <= kMaxPairs && h >= 1 && w >= 1 && (int64_t)h * w < (1LL << 30) && (int64_t)NSRC * n <= 65535;
+}
+
+// ---- the clauses the entry points' argument tests are built from
+inline bool random_source_ok(const int64_t* seeds, const float* rand, const int64_t* rand_offsets) {
+    return seeds || (rand && rand_offsets);
+}
+
+// the five outputs, the status word and the workspace are there, and the lists take the writer's 16-byte stores
+inline bool outputs_ok(const int64_t* idx_a, const int64_t* idx_b, const int64_t* offsets, const uint8_t* empty,
+                       const int32_t* type, const int32_t* status, const void* workspace) {
+    return idx_a && idx_b && offsets && empty && type && status && workspace && aligned16(idx_a) && aligned16(idx_b);
+}
+
+// The opening fills: the status word and, where matches are marked, the matched plane [n][hw] (to its 256-byte boundary)
+inline int begin(int32_t* status, uint8_t* matched, int n, int64_t hw, hipStream_t st) {
+    int rc = dcn::fill_bytes_async(status, 0, 4, st);
+    if (rc == DCN_OK && matched) rc = dcn::fill_bytes_async(matched, 0, align256((size_t)n * hw), st);
+    return rc;
 }
 
 inline Draws draws_of(int n, const int64_t* seeds, const float* rand, const int64_t* rand_offsets) {
@@ -547,21 +567,55 @@ inline Common common_of(const Workspace& ws, int n, int h, int w, int64_t attemp
     c.w = w;
     c.hw = (int64_t)h * w;
     c.attempts = attempts;
-    c.ls = c.hw > attempts ? c.hw : attempts;
+    c.ls = list_stride(c.hw, attempts);
     c.segs = segs_of(c.hw, attempts);
     c.src_mask = 0;
     return c;
 }
 
-inline OutArgs out_of(const Workspace& ws, int n, int h, int w, const int32_t* params, Draws d, int64_t* idx_a, int64_t* idx_b,
-                      int64_t cap, int64_t* offsets, uint8_t* empty, int32_t* type, int32_t* status, int data_type) {
+inline CandArgs cand_of(const Workspace& ws, const Common& c, const uint16_t* depth_a, const uint16_t* depth_b, const float* cams,
+                        Draws d, int32_t* status, int from_mask) {
+    CandArgs ca;
+    ca.depth_a = depth_a;
+    ca.depth_b = depth_b;
+    ca.cams = cams;
+    ca.d = d;
+    ca.flags = ws.flags;
+    ca.u2 = ws.u2;
+    ca.v2 = ws.v2;
+    ca.pix = ws.pix;
+    ca.list_a = ws.lists + (size_t)SRC_A0 * c.n * c.ls;
+    ca.count_a = ws.counts + (size_t)SRC_A0 * c.n;
+    ca.status = status;
+    ca.attempts = c.attempts;
+    ca.hw = c.hw;
+    ca.ls = c.ls;
+    ca.n = c.n;
+    ca.h = c.h;
+    ca.w = c.w;
+    ca.from_mask = from_mask;
+    return ca;
+}
+
+// mask a's pixel list (when the candidates come from it), the candidates, then the list of those that passed
+inline void find_candidates(const Common& c, const CandArgs& ca, hipStream_t st) {
+    if (ca.from_mask) compact(c, 1u << SRC_A0, st);
+    hipLaunchKernelGGL(candidate_kernel, dim3((unsigned)dcn::ceil_div64(c.attempts, kThreads), (unsigned)c.n), dim3(kThreads), 0,
+                       st, ca);
+    compact(c, 1u << SRC_FLAGS, st);
+}
+
+// The writer's arguments, within / complete form: `stride` match slots per pair in ma / mb, k1 / k2 non-matches per match,
+// `inv`: the background non-matches from 1 - mask b
+inline OutArgs out_of(const Workspace& ws, const Common& c, Draws d, int64_t* idx_a, int64_t* idx_b, int64_t cap, int64_t* offsets,
+                      uint8_t* empty, int32_t* type, int32_t* status, int data_type, int64_t stride, int k1, int k2, int inv) {
     OutArgs o;
     o.counts = ws.counts;
     o.mcount = ws.mcount;
     o.ma = ws.ma;
     o.mb = ws.mb;
     o.lists = ws.lists;
-    o.params = params;
+    o.params = c.params;
     o.d = d;
     o.offsets = offsets;
     o.empty = empty;
@@ -570,17 +624,27 @@ inline OutArgs out_of(const Workspace& ws, int n, int h, int w, const int32_t* p
     o.idx_a = idx_a;
     o.idx_b = idx_b;
     o.cap = cap;
-    o.hw = (int64_t)h * w;
-    o.ls = o.hw;                   // (within / complete: set by the caller when attempts > hw)
-    o.stride = 0;
+    o.hw = c.hw;
+    o.ls = c.ls;
+    o.stride = stride;
     o.samples = 0;
-    o.n = n;
-    o.h = h;
-    o.w = w;
-    o.k1 = o.k2 = 1;
+    o.n = c.n;
+    o.h = c.h;
+    o.w = c.w;
+    o.k1 = k1;
+    o.k2 = k2;
     o.across = 0;
-    o.inv = 0;
+    o.inv = inv;
     o.data_type = data_type;
+    return o;
+}
+
+// ... across form: `samples` pixels of each mask in the blind slot, nothing else
+inline OutArgs across_of(const Workspace& ws, const Common& c, Draws d, int64_t* idx_a, int64_t* idx_b, int64_t cap,
+                         int64_t* offsets, uint8_t* empty, int32_t* type, int32_t* status, int data_type, int64_t samples) {
+    OutArgs o = out_of(ws, c, d, idx_a, idx_b, cap, offsets, empty, type, status, data_type, 0, 1, 1, 0);
+    o.across = 1;
+    o.samples = samples;
     return o;
 }
 
@@ -679,7 +743,7 @@ __global__ void __launch_bounds__(kThreads) eval_select_kernel(EvalArgs a) {
 }
 
 // stages 4 - 6 after the matches (ma / mb / mcount / matched are in the workspace)
-inline int finish_within(const Workspace& ws, Common c, OutArgs o, hipStream_t st) {
+inline int finish_within(const Common& c, const OutArgs& o, hipStream_t st) {
     compact(c, (1u << SRC_BLIND) | (1u << SRC_MB) | (o.inv ? (1u << SRC_MBINV) : 0u), st);
     write_out(o, st);
     return dcn::check_launch();
@@ -704,39 +768,17 @@ extern "C" int dcn_eval_matches(int n, int h, int w, const uint16_t* depth_a, co
                                 int32_t* totals, int32_t* status, void* workspace, void* stream) {
     const int64_t hw = (int64_t)h * w;
     if (!shape_ok(n, h, w) || !depth_a || !depth_b || !mask_a || !cams || attempts < 1 || attempts > 4096 ||
-        (!seeds && (!rand || !rand_offsets)) || num_matches < 1 || (!match_order && !order_seeds) || !u_a || !v_a || !u_b ||
-        !v_b || !offsets || !totals || !status || !workspace)
+        !random_source_ok(seeds, rand, rand_offsets) || num_matches < 1 || (!match_order && !order_seeds) || !u_a || !v_a ||
+        !u_b || !v_b || !offsets || !totals || !status || !workspace)
         return DCN_E_INVALID;
     hipStream_t st = (hipStream_t)stream;
     Workspace ws;
     carve(&ws, (char*)workspace, n, hw, attempts, 1);
-    int rc = dcn::fill_bytes_async(status, 0, 4, st);
+    const int rc = begin(status, nullptr, n, hw, st);
     if (rc != DCN_OK) return rc;
-    Common c = common_of(ws, n, h, w, attempts, mask_a, mask_a, nullptr);
-    compact(c, 1u << SRC_A0, st);
-    const int64_t ls = hw > attempts ? hw : attempts;
-    CandArgs ca;
-    ca.depth_a = depth_a;
-    ca.depth_b = depth_b;
-    ca.cams = cams;
-    ca.d = draws_of(n, seeds, rand, rand_offsets);
-    ca.flags = ws.flags;
-    ca.u2 = ws.u2;
-    ca.v2 = ws.v2;
-    ca.pix = ws.pix;
-    ca.list_a = ws.lists + (size_t)SRC_A0 * n * ls;
-    ca.count_a = ws.counts + (size_t)SRC_A0 * n;
-    ca.status = status;
-    ca.attempts = attempts;
-    ca.hw = hw;
-    ca.ls = ls;
-    ca.n = n;
-    ca.h = h;
-    ca.w = w;
-    ca.from_mask = 1;
-    hipLaunchKernelGGL(candidate_kernel, dim3((unsigned)dcn::ceil_div64(attempts, kThreads), (unsigned)n), dim3(kThreads), 0, st,
-                       ca);
-    compact(c, 1u << SRC_FLAGS, st);
+    const Common c = common_of(ws, n, h, w, attempts, mask_a, mask_a, nullptr);
+    find_candidates(c, cand_of(ws, c, depth_a, depth_b, cams, draws_of(n, seeds, rand, rand_offsets), status, 1), st);
+    const int64_t ls = c.ls;
     EvalArgs e;
     e.sel = ws.lists + (size_t)SRC_FLAGS * n * ls;
     e.count = ws.counts + (size_t)SRC_FLAGS * n;
@@ -773,43 +815,18 @@ extern "C" int dcn_within_scene_samples(int n, int h, int w, const uint16_t* dep
     const int64_t hw = (int64_t)h * w;
     if (!shape_ok(n, h, w) || !depth_a || !depth_b || !mask_a || !mask_b || !cams || attempts < 1 || attempts > (1LL << 30) ||
         k_masked < 1 || k_background < 1 || (flags & ~(DCN_SAMPLE_ONLY_OFF_MASK | DCN_SAMPLE_MASK_INV)) ||
-        (!seeds && (!rand || !rand_offsets)) || !idx_a || !idx_b || !offsets || !empty || !type || !status || !workspace ||
-        capacity != (int64_t)n * (attempts * (1 + (int64_t)k_masked + k_background) + hw) ||
-        !aligned16(idx_a) || !aligned16(idx_b))
+        !random_source_ok(seeds, rand, rand_offsets) || !outputs_ok(idx_a, idx_b, offsets, empty, type, status, workspace) ||
+        capacity != (int64_t)n * (attempts * (1 + (int64_t)k_masked + k_background) + hw))
         return DCN_E_INVALID;
     hipStream_t st = (hipStream_t)stream;
     Workspace ws;
     carve(&ws, (char*)workspace, n, hw, attempts, attempts);
-    Draws d = draws_of(n, seeds, rand, rand_offsets);
-    int rc = dcn::fill_bytes_async(status, 0, 4, st);
-    if (rc == DCN_OK) rc = dcn::fill_bytes_async(ws.matched, 0, align256((size_t)n * hw), st);
+    const Draws d = draws_of(n, seeds, rand, rand_offsets);
+    const int rc = begin(status, ws.matched, n, hw, st);
     if (rc != DCN_OK) return rc;
-    Common c = common_of(ws, n, h, w, attempts, mask_a, mask_b, aug_params);
-    const int from_mask = (flags & DCN_SAMPLE_ONLY_OFF_MASK) ? 1 : 0;
-    if (from_mask) compact(c, 1u << SRC_A0, st);
-    CandArgs ca;
-    ca.depth_a = depth_a;
-    ca.depth_b = depth_b;
-    ca.cams = cams;
-    ca.d = d;
-    ca.flags = ws.flags;
-    ca.u2 = ws.u2;
-    ca.v2 = ws.v2;
-    ca.pix = ws.pix;
-    const int64_t ls = hw > attempts ? hw : attempts;
-    ca.list_a = ws.lists + (size_t)SRC_A0 * n * ls;
-    ca.count_a = ws.counts + (size_t)SRC_A0 * n;
-    ca.status = status;
-    ca.attempts = attempts;
-    ca.hw = hw;
-    ca.ls = ls;
-    ca.n = n;
-    ca.h = h;
-    ca.w = w;
-    ca.from_mask = from_mask;
-    hipLaunchKernelGGL(candidate_kernel, dim3((unsigned)dcn::ceil_div64(attempts, kThreads), (unsigned)n), dim3(kThreads), 0, st,
-                       ca);
-    compact(c, 1u << SRC_FLAGS, st);
+    const Common c = common_of(ws, n, h, w, attempts, mask_a, mask_b, aug_params);
+    find_candidates(c, cand_of(ws, c, depth_a, depth_b, cams, d, status, (flags & DCN_SAMPLE_ONLY_OFF_MASK) ? 1 : 0), st);
+    const int64_t ls = c.ls;
     MatchArgs m = {};
     m.sel = ws.lists + (size_t)SRC_FLAGS * n * ls;
     m.count = ws.counts + (size_t)SRC_FLAGS * n;
@@ -830,13 +847,8 @@ extern "C" int dcn_within_scene_samples(int n, int h, int w, const uint16_t* dep
     m.h = h;
     m.w = w;
     hipLaunchKernelGGL(match_kernel, dim3((unsigned)dcn::ceil_div64(attempts, kThreads), (unsigned)n), dim3(kThreads), 0, st, m);
-    OutArgs o = out_of(ws, n, h, w, aug_params, d, idx_a, idx_b, capacity, offsets, empty, type, status, data_type);
-    o.stride = attempts;
-    o.ls = ls;
-    o.k1 = k_masked;
-    o.k2 = k_background;
-    o.inv = (flags & DCN_SAMPLE_MASK_INV) ? 1 : 0;
-    return finish_within(ws, c, o, st);
+    return finish_within(c, out_of(ws, c, d, idx_a, idx_b, capacity, offsets, empty, type, status, data_type, attempts, k_masked,
+                                   k_background, (flags & DCN_SAMPLE_MASK_INV) ? 1 : 0), st);
 }
 
 extern "C" int dcn_complete_samples(int n, int h, int w, const int64_t* u_a, const int64_t* v_a, const void* u_b,
@@ -849,18 +861,15 @@ extern "C" int dcn_complete_samples(int n, int h, int w, const int64_t* u_a, con
     const int64_t hw = (int64_t)h * w;
     if (!shape_ok(n, h, w) || count < 0 || (count > 0 && (!u_a || !v_a || !u_b || !v_b)) || !list_offsets || !mask_a ||
         !mask_b || k_masked < 1 || k_background < 1 || (flags & ~DCN_SAMPLE_MASK_INV) ||
-        (uv_b_dtype != DCN_UV_INT64 && uv_b_dtype != DCN_UV_FLOAT32) || (!seeds && (!rand || !rand_offsets)) || !idx_a ||
-        !idx_b || !offsets || !empty || !type || !status || !workspace ||
-        capacity != count * (1 + (int64_t)k_masked + k_background) + (int64_t)n * hw ||
-        !aligned16(idx_a) || !aligned16(idx_b))
+        (uv_b_dtype != DCN_UV_INT64 && uv_b_dtype != DCN_UV_FLOAT32) || !random_source_ok(seeds, rand, rand_offsets) ||
+        !outputs_ok(idx_a, idx_b, offsets, empty, type, status, workspace) ||
+        capacity != count * (1 + (int64_t)k_masked + k_background) + (int64_t)n * hw)
         return DCN_E_INVALID;
     hipStream_t st = (hipStream_t)stream;
     const int64_t stride = count > 0 ? count : 1;
     Workspace ws;
     carve(&ws, (char*)workspace, n, hw, 0, stride);
-    Draws d = draws_of(n, seeds, rand, rand_offsets);
-    int rc = dcn::fill_bytes_async(status, 0, 4, st);
-    if (rc == DCN_OK) rc = dcn::fill_bytes_async(ws.matched, 0, align256((size_t)n * hw), st);
+    const int rc = begin(status, ws.matched, n, hw, st);
     if (rc != DCN_OK) return rc;
     MatchArgs m = {};
     m.ua = u_a;
@@ -882,13 +891,9 @@ extern "C" int dcn_complete_samples(int n, int h, int w, const int64_t* u_a, con
     m.h = h;
     m.w = w;
     hipLaunchKernelGGL(match_kernel, dim3((unsigned)dcn::ceil_div64(stride, kThreads), (unsigned)n), dim3(kThreads), 0, st, m);
-    Common c = common_of(ws, n, h, w, 0, mask_a, mask_b, aug_params);
-    OutArgs o = out_of(ws, n, h, w, aug_params, d, idx_a, idx_b, capacity, offsets, empty, type, status, data_type);
-    o.stride = stride;
-    o.k1 = k_masked;
-    o.k2 = k_background;
-    o.inv = (flags & DCN_SAMPLE_MASK_INV) ? 1 : 0;
-    return finish_within(ws, c, o, st);
+    const Common c = common_of(ws, n, h, w, 0, mask_a, mask_b, aug_params);
+    return finish_within(c, out_of(ws, c, draws_of(n, seeds, rand, rand_offsets), idx_a, idx_b, capacity, offsets, empty, type,
+                                   status, data_type, stride, k_masked, k_background, (flags & DCN_SAMPLE_MASK_INV) ? 1 : 0), st);
 }
 
 extern "C" int dcn_across_scene_samples(int n, int h, int w, const uint8_t* mask_a, const uint8_t* mask_b, int64_t num_samples,
@@ -896,22 +901,19 @@ extern "C" int dcn_across_scene_samples(int n, int h, int w, const uint8_t* mask
                                         const int64_t* rand_offsets, int data_type, int64_t* idx_a, int64_t* idx_b,
                                         int64_t capacity, int64_t* offsets, uint8_t* empty, int32_t* type, int32_t* status,
                                         void* workspace, void* stream) {
-    if (!shape_ok(n, h, w) || !mask_a || !mask_b || num_samples < 1 || (!seeds && (!rand || !rand_offsets)) || !idx_a ||
-        !idx_b || !offsets || !empty || !type || !status || !workspace || capacity != (int64_t)n * num_samples ||
-        !aligned16(idx_a) || !aligned16(idx_b))
+    const int64_t hw = (int64_t)h * w;
+    if (!shape_ok(n, h, w) || !mask_a || !mask_b || num_samples < 1 || !random_source_ok(seeds, rand, rand_offsets) ||
+        !outputs_ok(idx_a, idx_b, offsets, empty, type, status, workspace) || capacity != (int64_t)n * num_samples)
         return DCN_E_INVALID;
     hipStream_t st = (hipStream_t)stream;
     Workspace ws;
-    carve(&ws, (char*)workspace, n, (int64_t)h * w, 0, 0);
-    const int rc = dcn::fill_bytes_async(status, 0, 4, st);
+    carve(&ws, (char*)workspace, n, hw, 0, 0);
+    const int rc = begin(status, nullptr, n, hw, st);
     if (rc != DCN_OK) return rc;
-    Common c = common_of(ws, n, h, w, 0, mask_a, mask_b, aug_params);
+    const Common c = common_of(ws, n, h, w, 0, mask_a, mask_b, aug_params);
     compact(c, (1u << SRC_A0) | (1u << SRC_B0), st);
-    OutArgs o = out_of(ws, n, h, w, aug_params, draws_of(n, seeds, rand, rand_offsets), idx_a, idx_b, capacity, offsets, empty,
-                       type, status, data_type);
-    o.across = 1;
-    o.samples = num_samples;
-    write_out(o, st);
+    write_out(across_of(ws, c, draws_of(n, seeds, rand, rand_offsets), idx_a, idx_b, capacity, offsets, empty, type, status,
+                        data_type, num_samples), st);
     return dcn::check_launch();
 }
 

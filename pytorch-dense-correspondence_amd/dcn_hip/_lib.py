@@ -289,3 +289,8 @@ def stream_ptr():
 
 def ptr(t):
     return None if t is None else c_void_p(t.data_ptr())
+
+
+def host_ptr(a):
+    """A contiguous numpy array the library reads on the host"""
+    return a.ctypes.data_as(c_void_p)

@@ -17,11 +17,11 @@ import collections
 import numpy as np
 import torch
 
-from . import _lib
+from . import _args, _lib
 
 PARAM_WORDS = 16
 FLIP_V, FLIP_H, RANDOMIZE, GRADIENT, VERTICAL, NOISE = 1, 2, 4, 8, 16, 32
-UV_INT64, UV_FLOAT32 = 0, 1
+UV_INT64, UV_FLOAT32 = _args.UV_INT64, _args.UV_FLOAT32
 
 DEFAULT_IMAGE_MEAN = [0.5573105812072754, 0.37420374155044556, 0.37020164728164673]   # constants.py:11-12
 DEFAULT_IMAGE_STD_DEV = [0.24336038529872894, 0.2987397611141205, 0.31875079870224]
@@ -43,25 +43,6 @@ def draw_params(num_images, device, generator=None, domain_randomize=True, flip=
     return torch.cat([flags.view(-1, 1), colours, zeros, seeds, zeros.expand(num_images, 6)], dim=1).contiguous()
 
 
-def _f32x3(v):
-    a = np.ascontiguousarray(np.asarray(v, dtype=np.float32).reshape(-1))
-    if a.size != 3:
-        raise ValueError("mean / std need 3 entries, got %d" % a.size)
-    return a
-
-
-def _hp(a):
-    return a.ctypes.data_as(_lib.c_void_p)
-
-
-def _uv_dtype(t):
-    if t.dtype == torch.int64:
-        return UV_INT64
-    if t.dtype == torch.float32:
-        return UV_FLOAT32
-    raise TypeError("pixel lists must be int64 or float32 tensors, got %s" % t.dtype)
-
-
 def flip_uv(uv, h, w, params=None, offsets=None, flags=FLIP_V | FLIP_H):
     """(u, v) -> ((w-1) - u, (h-1) - v) per the FLIP_H / FLIP_V bits of each entry's image (``params`` records, entries of image b
     at ``offsets[b]:offsets[b+1]``) or of ``flags``.  dtype kept (int64 / float32)."""
@@ -79,7 +60,7 @@ def flip_uv(uv, h, w, params=None, offsets=None, flags=FLIP_V | FLIP_H):
         raise ValueError("flip_uv: offsets need >= 2 entries and params one contiguous int32 record per image")
     if offsets is not None and (offsets.dtype != torch.int64 or not offsets.is_contiguous()):
         raise ValueError("flip_uv: offsets must be a contiguous int64 tensor")
-    rc = lib.dcn_flip_uv(_uv_dtype(u), _lib.ptr(u), _lib.ptr(v), _lib.ptr(uo), _lib.ptr(vo), u.numel(), n, _lib.ptr(offsets),
+    rc = lib.dcn_flip_uv(_args.uv_dtype(u), _lib.ptr(u), _lib.ptr(v), _lib.ptr(uo), _lib.ptr(vo), u.numel(), n, _lib.ptr(offsets),
                          _lib.ptr(params), int(flags), int(h), int(w), _lib.stream_ptr())
     _lib.check(rc, "dcn_flip_uv")
     return uo, vo
@@ -115,12 +96,7 @@ def augment_images(rgb_a, mask_a, params, rgb_b=None, mask_b=None, noise=None, m
     n, h, w = int(rgb_a.shape[0]), int(rgb_a.shape[1]), int(rgb_a.shape[2])
     args, out = {}, {}
     for s, rgb, mask in sides:
-        if rgb.dtype != torch.uint8 or tuple(rgb.shape) != (n, h, w, 3):
-            raise ValueError("images must be uint8 [N, H, W, 3] of one shape, got %s %s" % (rgb.dtype, tuple(rgb.shape)))
-        if mask is None or tuple(mask.shape) != (n, h, w):
-            raise ValueError("masks must be [N, H, W] matching their images")
-        rgb = rgb.contiguous()
-        mask = (mask if mask.dtype == torch.uint8 else mask.to(torch.uint8)).contiguous()
+        rgb, mask = _args.image(rgb, n, h, w, "rgb_" + s), _args.mask(mask, n, h, w, "mask_" + s)
         _lib.require_device(rgb, mask)
         args["rgb_" + s], args["mask_" + s] = rgb, mask
         dev = rgb.device
@@ -137,9 +113,9 @@ def augment_images(rgb_a, mask_a, params, rgb_b=None, mask_b=None, noise=None, m
     _lib.require_device(params, noise)
     g = lambda k: _lib.ptr(args.get(k))
     o = lambda k: _lib.ptr(out.get(k))
-    m, sd = _f32x3(mean), _f32x3(std)
+    m, sd = _args.mean_std(mean), _args.mean_std(std)
     rc = lib.dcn_augment_images(n, h, w, g("rgb_a"), g("rgb_b"), g("mask_a"), g("mask_b"), _lib.ptr(params),
-                                _lib.ptr(noise), _hp(m), _hp(sd), o("input_a"),
+                                _lib.ptr(noise), _lib.host_ptr(m), _lib.host_ptr(sd), o("input_a"),
                                 o("input_b"), o("rgb_a"), o("rgb_b"), o("mask_a"), o("mask_b"), _lib.stream_ptr())
     _lib.check(rc, "dcn_augment_images")
     return out
@@ -150,11 +126,7 @@ def _offsets(offsets, n, dev):
         if n != 1:
             raise ValueError("offsets [B + 1] are needed to split concatenated pixel lists over B = %d images" % n)
         return None
-    if not torch.is_tensor(offsets):
-        offsets = torch.tensor([int(o) for o in offsets], dtype=torch.int64)
-    if offsets.numel() != n + 1:
-        raise ValueError("offsets must have B + 1 = %d entries, got %d" % (n + 1, offsets.numel()))
-    return offsets.to(device=dev, dtype=torch.int64, non_blocking=True).contiguous()
+    return _args.offsets(offsets, n, dev)
 
 
 def augment_image_pairs(rgb_a, rgb_b, mask_a, mask_b, uv_a=None, uv_b=None, offsets=None, *, domain_randomize=True,

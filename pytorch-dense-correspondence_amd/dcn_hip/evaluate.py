@@ -14,15 +14,15 @@ copies the table to the host once.
 frames of the store, for the whole image and for the object mask, written to ``descriptor_statistics.yaml``.
 """
 import collections
-import ctypes
 import os
 
 import numpy as np
 import torch
 
-from . import _lib
+from . import _args, _lib
 from . import augment as _aug
-from .samples import CAM_FLOATS, _depth, _mask, _random, draw_seeds
+from .frames import gather_frames
+from .samples import random_source
 
 COLUMNS = ("norm_diff_descriptor_ground_truth", "norm_diff_descriptor", "norm_diff_descriptor_masked",
            "norm_diff_ground_truth_3d", "norm_diff_pred_3d", "norm_diff_pred_3d_masked", "pixel_match_error_l2",
@@ -71,11 +71,9 @@ def match_statistics_pairs(res_a, res_b, mask_b, depth_a, depth_b, cams, u_a, v_
     if d < 1 or d > 64:
         raise ValueError("descriptor dimension must be 1 .. 64, got %d" % d)
     ra, rb = res_a.contiguous().float(), res_b.contiguous().float()
-    mb = _mask(mask_b, P, h, w, "mask_b")
-    da, db = _depth(depth_a, P, h, w, "depth_a"), _depth(depth_b, P, h, w, "depth_b")
-    if tuple(cams.shape) != (P, CAM_FLOATS) or cams.dtype != torch.float32:
-        raise ValueError("cams must be float32 [%d, %d], got %s %s" % (P, CAM_FLOATS, cams.dtype, tuple(cams.shape)))
-    cams = cams.contiguous()
+    mb = _args.mask(mask_b, P, h, w, "mask_b")
+    da, db = _args.depth(depth_a, P, h, w, "depth_a"), _args.depth(depth_b, P, h, w, "depth_b")
+    cams = _args.camera_rows(cams, P, "cams")
     ua = _rows(u_a, torch.int64, "u_a")
     R = int(ua.numel())
     va, ub, vb = _rows(v_a, torch.int64, "v_a", R), _rows(u_b, torch.float32, "u_b", R), _rows(v_b, torch.float32, "v_b", R)
@@ -126,28 +124,15 @@ def find_eval_matches(depth_a, depth_b, mask_a, cams, num_matches=100, *, num_at
     lib = _lib.get()
     n, h, w = int(mask_a.shape[0]), int(mask_a.shape[1]), int(mask_a.shape[2])
     dev = mask_a.device
-    da, db = _depth(depth_a, n, h, w, "depth_a"), _depth(depth_b, n, h, w, "depth_b")
-    ma = _mask(mask_a, n, h, w, "mask_a")
+    da, db = _args.depth(depth_a, n, h, w, "depth_a"), _args.depth(depth_b, n, h, w, "depth_b")
+    ma = _args.mask(mask_a, n, h, w, "mask_a")
     A, M = int(num_attempts), int(num_matches)
     if A < 1 or A > 4096 or M < 1 or n > 1024:
         raise ValueError("num_attempts must be 1 .. 4096, num_matches >= 1 and at most 1024 pairs per call")
-    if tuple(cams.shape) != (n, CAM_FLOATS) or cams.dtype != torch.float32:
-        raise ValueError("cams must be float32 [%d, %d], got %s %s" % (n, CAM_FLOATS, cams.dtype, tuple(cams.shape)))
-    cams = cams.contiguous()
-    sd, rand, roff = _random(n, dev, generator, draws, seeds)
-    order = osd = None
-    if match_order is not None:
-        order = torch.as_tensor(np.asarray(match_order.cpu() if torch.is_tensor(match_order) else match_order,
-                                           np.int64).astype(np.int32))
-        if tuple(order.shape) != (n, M):
-            raise ValueError("match_order must be [%d, %d] (-1 padded), got %s" % (n, M, tuple(order.shape)))
-        order = order.to(dev).contiguous()
-    elif order_seeds is None:
-        osd = draw_seeds(n, dev, generator)
-    else:
-        osd = torch.as_tensor(order_seeds).to(device=dev, dtype=torch.int64).contiguous().view(-1)
-        if osd.numel() != n:
-            raise ValueError("order_seeds must hold one int64 per pair (%d)" % n)
+    cams = _args.camera_rows(cams, n, "cams")
+    sd, rand, roff = random_source(n, dev, generator, draws, seeds)
+    order = None if match_order is None else _args.replay_table(match_order, (n, M), "match_order", dev)
+    osd = None if match_order is not None else _args.seeds_for(n, dev, generator, order_seeds, "order_seeds")
     _lib.require_device(da, db, ma, cams, sd, rand, roff, order, osd)
     cap = n * min(M, A)
     ua, va = torch.empty(cap, dtype=torch.int64, device=dev), torch.empty(cap, dtype=torch.int64, device=dev)
@@ -229,6 +214,34 @@ def _frame_pairs(store, pairs):
     return fr
 
 
+def _gather_host_frames(store, fr, want):
+    """``gather_frames`` of a host table ``fr`` (int [P, 2] store frame indices: slots 0 and 1) -> (rgb, depth, mask, cams,
+    status); status int32 [1], zero unless the gather rejected a frame index."""
+    P, dev = int(fr.shape[0]), store.device
+    frames = torch.from_numpy(np.concatenate([fr, np.full((P, 2), -1, np.int64)], axis=1).astype(np.int32)).to(dev)
+    status = torch.zeros(1, dtype=torch.int32, device=dev)
+    return gather_frames(store, frames, None, status, 2, want) + (status,)
+
+
+def _forward_in_eval_mode(dcn, rgb, mask, rgb_b, mask_b, step, mean, std, consume):
+    """``dcn`` in eval mode over the frames of ``rgb`` (pairs of frames with ``rgb_b``), ``step`` at a time: ToTensor +
+    Normalize by the augmentation kernel with every augmentation switched off (zero records), ``forward_image_tensors`` (a's
+    images, then b's), ``consume(lo, n, descriptors)``.  ``dcn.training`` is left as found."""
+    count, sides = int(rgb.shape[0]), 1 if rgb_b is None else 2
+    params = torch.zeros((sides * min(step, count), _aug.PARAM_WORDS), dtype=torch.int32, device=rgb.device)
+    was_training = dcn.training
+    dcn.eval()
+    try:
+        for lo in range(0, count, step):
+            n = min(step, count - lo)
+            b = {} if rgb_b is None else dict(rgb_b=rgb_b[lo:lo + n], mask_b=mask_b[lo:lo + n])
+            x = _aug.augment_images(rgb[lo:lo + n], mask[lo:lo + n], params[:sides * n], mean=mean, std=std, want_mask=False, **b)
+            x = x["input_a"] if rgb_b is None else torch.cat([x["input_a"], x["input_b"]])
+            consume(lo, n, dcn.forward_image_tensors(x))
+    finally:
+        dcn.train(was_training)
+
+
 def evaluate_frame_pairs(dcn, store, pairs, num_matches=100, *, generator=None, draws=None, match_order=None, batch_pairs=8,
                          mean=_aug.DEFAULT_IMAGE_MEAN, std=_aug.DEFAULT_IMAGE_STD_DEV):
     """The reference's per-pair evaluation for ``pairs`` ([P, 2] store frame indices (a, b), or choose_pairs' [P, 3]; P <=
@@ -243,34 +256,13 @@ def evaluate_frame_pairs(dcn, store, pairs, num_matches=100, *, generator=None, 
         raise ValueError("at most 1024 pairs per call, got %d" % P)
     if int(batch_pairs) < 1:
         raise ValueError("batch_pairs must be >= 1")
-    lib = _lib.get()
-    dev = store.device
-    h, w = store.h, store.w
-    frames = torch.from_numpy(np.concatenate([fr, np.full((P, 2), -1, np.int64)], axis=1).astype(np.int32)).to(dev)
-    rgb = torch.empty((2, P, h, w, 3), dtype=torch.uint8, device=dev)
-    depth = torch.empty((2, P, h, w), dtype=torch.int16, device=dev)
-    mask = torch.empty((2, P, h, w), dtype=torch.uint8, device=dev)
-    cams = torch.empty((1, P, CAM_FLOATS), dtype=torch.float32, device=dev)
-    status = torch.zeros(1, dtype=torch.int32, device=dev)
-    p = _lib.ptr
-    rc = lib.dcn_gather_frames(P, 2, ctypes.byref(store.desc), p(frames), None, p(rgb), p(depth), p(mask), p(cams), p(status),
-                               _lib.stream_ptr())
-    _lib.check(rc, "dcn_gather_frames")
-    was_training = dcn.training
-    dcn.eval()
-    try:
-        res = [[], []]
-        step = int(batch_pairs)
-        for lo in range(0, P, step):
-            n = min(step, P - lo)
-            params = torch.zeros((2 * n, _aug.PARAM_WORDS), dtype=torch.int32, device=dev)
-            x = _aug.augment_images(rgb[0, lo:lo + n], mask[0, lo:lo + n], params, rgb_b=rgb[1, lo:lo + n],
-                                    mask_b=mask[1, lo:lo + n], mean=mean, std=std, want_mask=False)
-            y = dcn.forward_image_tensors(torch.cat([x["input_a"], x["input_b"]]))
-            res[0].append(y[:n])
-            res[1].append(y[n:])
-    finally:
-        dcn.train(was_training)
+    rgb, depth, mask, cams, status = _gather_host_frames(store, fr, ("rgb", "depth", "mask", "cams"))
+    res = [[], []]
+
+    def keep(lo, n, y):
+        res[0].append(y[:n])
+        res[1].append(y[n:])
+    _forward_in_eval_mode(dcn, rgb[0], mask[0], rgb[1], mask[1], int(batch_pairs), mean, std, keep)
     res_a, res_b = torch.cat(res[0]).contiguous(), torch.cat(res[1]).contiguous()
     m = find_eval_matches(depth[0], depth[1], mask[0], cams[0], num_matches, generator=generator, draws=draws,
                           match_order=match_order)
@@ -341,7 +333,7 @@ def descriptor_statistics(res, mask):
         raise ValueError("res must hold 1 .. 65535 images of 1 <= H * W < 2^31 pixels, got %s" % (tuple(res.shape),))
     if mask.dtype not in (torch.uint8, torch.bool):
         raise ValueError("mask must be uint8 (or bool), got %s" % mask.dtype)
-    m = _mask(mask, n, h, w, "mask")
+    m = _args.mask(mask, n, h, w, "mask")
     r = res.contiguous()
     try:
         _lib.require_device(r, m)
@@ -432,38 +424,23 @@ def compute_descriptor_statistics_on_dataset(dcn, store, num_images=100, save_to
         filename = os.path.join(utils.convert_to_absolute_path(dcn.path_to_network_params_folder),
                                 "descriptor_statistics.yaml")
     chosen = choose_frames(store, n, host_rng)
-    lib = _lib.get()
     dev = store.device
     h, w = store.h, store.w
     # the gather copies pairs of frames: frames [0, P) in slot 0 and [P, n) in slot 1 (an odd n repeats the last frame), so
     # that the [2, P] planes, flattened, are the n frames in order
     P = (n + 1) // 2
     fr = np.concatenate([chosen[:, 1], chosen[-1:, 1]])[:2 * P].reshape(2, P).T
-    frames = torch.from_numpy(np.concatenate([fr, np.full((P, 2), -1, np.int64)], axis=1).astype(np.int32)).to(dev)
-    rgb = torch.empty((2, P, h, w, 3), dtype=torch.uint8, device=dev)
-    mask = torch.empty((2, P, h, w), dtype=torch.uint8, device=dev)
-    bad_frame = torch.zeros(1, dtype=torch.int32, device=dev)
-    p = _lib.ptr
-    rc = lib.dcn_gather_frames(P, 2, ctypes.byref(store.desc), p(frames), None, p(rgb), None, p(mask), None, p(bad_frame),
-                               _lib.stream_ptr())
-    _lib.check(rc, "dcn_gather_frames")
-    rgb, mask = rgb.view(2 * P, h, w, 3), mask.view(2 * P, h, w)
-    per_image = mask_pixels = None
-    params = torch.zeros((min(step, n), _aug.PARAM_WORDS), dtype=torch.int32, device=dev)   # (every augmentation off)
-    was_training = dcn.training
-    dcn.eval()
-    try:
-        for lo in range(0, n, step):
-            k = min(step, n - lo)
-            x = _aug.augment_images(rgb[lo:lo + k], mask[lo:lo + k], params[:k], want_mask=False)
-            res = dcn.forward_image_tensors(x["input_a"])
-            if per_image is None:
-                per_image = torch.empty((n, 2, 3, int(res.shape[3])), dtype=torch.float32, device=dev)
-                mask_pixels = torch.empty(n, dtype=torch.int32, device=dev)
-            per_image[lo:lo + k], mask_pixels[lo:lo + k] = descriptor_statistics(res, mask[lo:lo + k])
-    finally:
-        dcn.train(was_training)
-    stats, used = combine_descriptor_statistics(per_image, mask_pixels, n)
+    rgb, _, mask, _, bad_frame = _gather_host_frames(store, fr, ("rgb", "mask"))
+    rgb, mask = rgb.view(2 * P, h, w, 3)[:n], mask.view(2 * P, h, w)[:n]
+    out = []
+
+    def statistics(lo, k, res):
+        if not out:
+            out.extend([torch.empty((n, 2, 3, int(res.shape[3])), dtype=torch.float32, device=dev),
+                        torch.empty(n, dtype=torch.int32, device=dev)])
+        out[0][lo:lo + k], out[1][lo:lo + k] = descriptor_statistics(res, mask[lo:lo + k])
+    _forward_in_eval_mode(dcn, rgb, mask, None, None, step, _aug.DEFAULT_IMAGE_MEAN, _aug.DEFAULT_IMAGE_STD_DEV, statistics)
+    stats, used = combine_descriptor_statistics(out[0], out[1], n)
     # one transfer: the statistics, the number of images used and the gather's status word in one float64 block
     block = torch.cat([stats.double().view(-1), used.double(), bad_frame.double()]).cpu().numpy()
     if int(block[-1]) != 0:

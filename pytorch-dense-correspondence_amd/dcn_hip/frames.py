@@ -15,10 +15,10 @@ import ctypes
 import numpy as np
 import torch
 
-from . import _lib
+from . import _args, _lib
 from .samples import (CAM_FLOATS, DIFFERENT_OBJECT, MULTI_OBJECT, SINGLE_OBJECT_ACROSS_SCENE, SINGLE_OBJECT_WITHIN_SCENE,
-                      SYNTHETIC_MULTI_OBJECT, _f32, build_across_scene_samples, build_within_scene_samples,
-                      concat_sample_batches, draw_seeds, options_from_config)
+                      SYNTHETIC_MULTI_OBJECT, build_across_scene_samples, build_within_scene_samples, concat_sample_batches,
+                      options_from_config)
 
 BAD_INDEX, BAD_DRAWS, NO_CANDIDATES = 1, 2, 4
 SLOTS = 4
@@ -58,13 +58,9 @@ class FrameStore(object):
         if S < 1 or len(first) != S + 1 or first[0] != 0 or any(b <= a for a, b in zip(first, first[1:])):
             raise ValueError("scene_first_frame must be [S + 1] increasing from 0, every scene with >= 1 frame")
         F = first[-1]
-        if rgb.dim() != 4 or rgb.shape[3] != 3 or rgb.dtype != torch.uint8 or int(rgb.shape[0]) != F:
-            raise ValueError("rgb must be uint8 [%d, H, W, 3], got %s %s" % (F, rgb.dtype, tuple(rgb.shape)))
+        rgb = _args.image(rgb, F, None, None, "rgb")
         h, w = int(rgb.shape[1]), int(rgb.shape[2])
-        if tuple(depth.shape) != (F, h, w) or depth.element_size() != 2 or depth.is_floating_point():
-            raise ValueError("depth must be 16-bit integer [%d, %d, %d] millimetres" % (F, h, w))
-        if tuple(mask.shape) != (F, h, w):
-            raise ValueError("mask must be [%d, %d, %d]" % (F, h, w))
+        depth, mask = _args.depth(depth, F, h, w, "depth"), _args.mask(mask, F, h, w, "mask")
         if tuple(poses.shape) != (F, 4, 4):
             raise ValueError("poses must be [%d, 4, 4]" % F)
         O = max(sobj) + 1 if sobj else 0
@@ -75,22 +71,13 @@ class FrameStore(object):
             raise ValueError("objects must be numbered 0 .. O - 1, each with at least one scene")
         self.device = rgb.device
         dev = self.device
-        self.rgb = rgb.contiguous()
-        self.depth = (depth if depth.dtype == torch.int16 else depth.view(torch.int16)).contiguous()
-        self.mask = (mask if mask.dtype == torch.uint8 else mask.to(torch.uint8)).contiguous()
+        self.rgb, self.mask = rgb, mask
+        self.depth = depth if depth.dtype == torch.int16 else depth.view(torch.int16)
         self.poses = torch.as_tensor(poses, dtype=torch.float64).to(dev).reshape(F, 16).contiguous()
         # host copy of the frame translations, float64 [F, 3] (evaluate.choose_pairs)
         self.translations_host = self.poses.view(F, 4, 4)[:, :3, 3].cpu().numpy().copy()
-        if K is None:
-            from dense_correspondence.correspondence_tools.correspondence_finder import get_default_K_matrix
-            K = get_default_K_matrix()
-        K = np.asarray(K.cpu() if torch.is_tensor(K) else K, dtype=np.float64)
-        Ks = np.broadcast_to(K, (S, 3, 3)) if K.shape == (3, 3) else K
-        if Ks.shape != (S, 3, 3):
-            raise ValueError("K must be [3, 3] or [%d, 3, 3], got %s" % (S, K.shape))
+        Ks, cams = _args.camera_k_rows(K, S)                 # (K | K^-1 per scene: the first 18 floats of a camera row)
         self.K = np.array(Ks, dtype=np.float64)
-        # K, K^-1 per scene exactly as samples._cameras builds them
-        cams = np.stack([np.concatenate([_f32(k).reshape(-1), _f32(np.linalg.inv(k)).reshape(-1)]) for k in Ks])
         self.scene_cams = torch.from_numpy(np.ascontiguousarray(cams, dtype=np.float32)).to(dev)
         i32 = lambda l: torch.tensor(l if l else [0], dtype=torch.int32).to(dev)
         self.scene_first_frame_host, self.scene_object_host = first, sobj
@@ -234,19 +221,8 @@ def select_frames(store, batch_size, data_type, *, generator=None, seeds=None, d
         raise ValueError("batch_size and num_attempts must be >= 1")
     dev = store.device
     lib = _lib.get()
-    if draws is not None:
-        dr = torch.as_tensor(np.asarray(draws.cpu() if torch.is_tensor(draws) else draws, np.int64).astype(np.int32))
-        if tuple(dr.shape) != (n, draw_words(A)):
-            raise ValueError("draws must be [%d, %d], got %s" % (n, draw_words(A), tuple(dr.shape)))
-        dr, sd = dr.to(dev), None
-    else:
-        dr = None
-        if seeds is None:
-            sd = draw_seeds(n, dev, generator)
-        else:
-            sd = torch.as_tensor(seeds).to(device=dev, dtype=torch.int64).contiguous().view(-1)
-            if sd.numel() != n:
-                raise ValueError("seeds must hold one int64 per pair (%d)" % n)
+    dr = None if draws is None else _args.replay_table(draws, (n, draw_words(A)), "draws", dev)
+    sd = None if draws is not None else _args.seeds_for(n, dev, generator, seeds)
     frames = torch.empty((n, SLOTS), dtype=torch.int32, device=dev)
     empty = torch.empty(n, dtype=torch.bool, device=dev)
     scenes = torch.empty((n, 2), dtype=torch.int32, device=dev)
@@ -260,16 +236,26 @@ def select_frames(store, batch_size, data_type, *, generator=None, seeds=None, d
     _lib.check(rc, "dcn_select_frames")
     rgb = depth = mask = cams = None
     if gather:
-        k = 4 if t == SYNTHETIC_MULTI_OBJECT else 2
-        H, W = store.h, store.w
-        rgb = torch.empty((k, n, H, W, 3), dtype=torch.uint8, device=dev)
-        depth = torch.empty((k, n, H, W), dtype=torch.int16, device=dev)
-        mask = torch.empty((k, n, H, W), dtype=torch.uint8, device=dev)
-        cams = torch.empty((k // 2, n, CAM_FLOATS), dtype=torch.float32, device=dev)
-        rc = lib.dcn_gather_frames(n, k, desc, P(frames), P(empty), P(rgb), P(depth), P(mask), P(cams), P(status),
-                                   _lib.stream_ptr())
-        _lib.check(rc, "dcn_gather_frames")
+        rgb, depth, mask, cams = gather_frames(store, frames, empty, status, 4 if t == SYNTHETIC_MULTI_OBJECT else 2)
     return FrameBatch(t, frames, empty, scenes, objects, status, sd, rgb, depth, mask, cams)
+
+
+def gather_frames(store, frames, empty, status, k=2, want=("rgb", "depth", "mask", "cams")):
+    """One ``dcn_gather_frames`` launch: slots 0 .. k - 1 of ``frames`` (int32 [n, 4] store frame indices on the device) into
+    new batch tensors rgb uint8 [k, n, H, W, 3], depth int16 [k, n, H, W], mask uint8 [k, n, H, W] and cams fp32 [k / 2, n, 50]
+    (None for what is not in ``want``).  ``empty`` (bool [n] or None): pairs whose depth is zeroed; ``status`` (int32 [1]):
+    BAD_INDEX is OR-ed into it for a frame index outside the store.  -> (rgb, depth, mask, cams)."""
+    n, H, W, dev = int(frames.shape[0]), store.h, store.w, store.device
+    new = lambda name, shape, dtype: torch.empty(shape, dtype=dtype, device=dev) if name in want else None
+    rgb = new("rgb", (k, n, H, W, 3), torch.uint8)
+    depth = new("depth", (k, n, H, W), torch.int16)
+    mask = new("mask", (k, n, H, W), torch.uint8)
+    cams = new("cams", (k // 2, n, CAM_FLOATS), torch.float32)
+    P = _lib.ptr
+    rc = _lib.get().dcn_gather_frames(n, k, ctypes.byref(store.desc), P(frames), P(empty), P(rgb), P(depth), P(mask), P(cams),
+                                      P(status), _lib.stream_ptr())
+    _lib.check(rc, "dcn_gather_frames")
+    return rgb, depth, mask, cams
 
 
 def data_type_distribution(training_config):

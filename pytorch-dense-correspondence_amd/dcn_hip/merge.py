@@ -13,8 +13,8 @@ import collections
 
 import torch
 
-from . import _lib
-from .augment import DEFAULT_IMAGE_MEAN, DEFAULT_IMAGE_STD_DEV, _f32x3, _hp
+from . import _args, _lib
+from .augment import DEFAULT_IMAGE_MEAN, DEFAULT_IMAGE_STD_DEV
 
 FG_A, FG_B = 0, 1
 DROP_EMPTY = 1
@@ -29,18 +29,8 @@ def draw_foreground(num_samples, device, generator=None):
     return torch.randint(0, 2, (num_samples, 2), device=device, generator=generator, dtype=torch.int32)
 
 
-def _image(t, n, h, w, what):
-    if t.dtype != torch.uint8 or tuple(t.shape) != (n, h, w, 3):
-        raise ValueError("%s must be uint8 [%d, %d, %d, 3], got %s %s" % (what, n, h, w, t.dtype, tuple(t.shape)))
-    return t.contiguous()
-
-
 def _mask(t, n, h, w, what):
-    if t is None:
-        return None
-    if tuple(t.shape) != (n, h, w):
-        raise ValueError("%s must be [%d, %d, %d], got %s" % (what, n, h, w, tuple(t.shape)))
-    return (t if t.dtype == torch.uint8 else t.to(torch.uint8)).contiguous()
+    return None if t is None else _args.mask(t, n, h, w, what)
 
 
 def _foreground(fg, n, dev):
@@ -59,8 +49,8 @@ def merge_images(rgb_a, rgb_b, mask_a, mask_b, foreground, frames=1, mean=DEFAUL
     n, h, w = int(rgb_a[0].shape[0]), int(rgb_a[0].shape[1]), int(rgb_a[0].shape[2])
     if frames not in (1, 2) or not all(len(x) == frames for x in (rgb_a, rgb_b, mask_a, mask_b)):
         raise ValueError("merge_images: 1 or 2 frames, one image and mask per object and frame")
-    ia = [_image(t, n, h, w, "rgb_a") for t in rgb_a]
-    ib = [_image(t, n, h, w, "rgb_b") for t in rgb_b]
+    ia = [_args.image(t, n, h, w, "rgb_a") for t in rgb_a]
+    ib = [_args.image(t, n, h, w, "rgb_b") for t in rgb_b]
     ma = [_mask(t, n, h, w, "mask_a") for t in mask_a]
     mb = [_mask(t, n, h, w, "mask_b") for t in mask_b]
     if foreground.dtype != torch.int32 or tuple(foreground.shape) != (n, 2) or not foreground.is_contiguous():
@@ -71,9 +61,9 @@ def merge_images(rgb_a, rgb_b, mask_a, mask_b, foreground, frames=1, mean=DEFAUL
            "mask": [torch.empty(n, h, w, dtype=torch.float32, device=dev) if want_mask else None for _ in range(frames)],
            "rgb": [torch.empty(n, h, w, 3, dtype=torch.uint8, device=dev) if want_rgb else None for _ in range(frames)]}
     f2 = lambda lst: _lib.ptr(lst[1]) if frames == 2 else None
-    m, sd = _f32x3(mean), _f32x3(std)
+    m, sd = _args.mean_std(mean), _args.mean_std(std)
     rc = lib.dcn_merge_images(n, frames, h, w, _lib.ptr(foreground), _lib.ptr(ia[0]), _lib.ptr(ib[0]), f2(ia), f2(ib),
-                              _lib.ptr(ma[0]), _lib.ptr(mb[0]), f2(ma), f2(mb), _hp(m), _hp(sd),
+                              _lib.ptr(ma[0]), _lib.ptr(mb[0]), f2(ma), f2(mb), _lib.host_ptr(m), _lib.host_ptr(sd),
                               _lib.ptr(out["input"][0]), f2(out["input"]), _lib.ptr(out["mask"][0]), f2(out["mask"]),
                               _lib.ptr(out["rgb"][0]), f2(out["rgb"]), _lib.stream_ptr())
     _lib.check(rc, "dcn_merge_images")
@@ -87,14 +77,6 @@ def _list(uv, what):
         raise ValueError("%s must be two int64 [N] tensors of one length, got %s %s / %s %s"
                          % (what, u.dtype, tuple(u.shape), v.dtype, tuple(v.shape)))
     return u.contiguous(), v.contiguous()
-
-
-def _offsets(offsets, n, dev, what):
-    if not torch.is_tensor(offsets):
-        offsets = torch.tensor([int(o) for o in offsets], dtype=torch.int64)
-    if offsets.numel() != n + 1:
-        raise ValueError("%s must have B + 1 = %d entries, got %d" % (what, n + 1, offsets.numel()))
-    return offsets.to(device=dev, dtype=torch.int64, non_blocking=True).contiguous().view(-1)
 
 
 def prune_and_concat(h, w, foreground, list_a, list_b, masks, drop_empty=True):
@@ -156,8 +138,8 @@ def merge_synthetic_samples(rgb_a1, rgb_a2, rgb_b1, rgb_b2, mask_a1, mask_a2, ma
     ma1, ma2, mb1, mb2 = masks
     out = merge_images([rgb_a1, rgb_a2], [rgb_b1, rgb_b2], [ma1, ma2], [mb1, mb2], foreground, frames=2, mean=mean, std=std,
                        want_rgb=return_rgb)
-    la = (uv_a1, uv_a2, _offsets(offsets_a, n, dev, "offsets_a"), int(uv_a1[0].numel()))
-    lb = (uv_b1, uv_b2, _offsets(offsets_b, n, dev, "offsets_b"), int(uv_b1[0].numel()))
+    la = (uv_a1, uv_a2, _args.offsets(offsets_a, n, dev, "offsets_a"), int(uv_a1[0].numel()))
+    lb = (uv_b1, uv_b2, _args.offsets(offsets_b, n, dev, "offsets_b"), int(uv_b1[0].numel()))
     uv_1, uv_2, offsets, empty, status = prune_and_concat(
         h, w, foreground, la, lb, {(1, "a"): ma1, (1, "b"): mb1, (2, "a"): ma2, (2, "b"): mb2})
     return MergedSamples(out["input"][0], out["input"][1], out["mask"][0], out["mask"][1], uv_1, uv_2, offsets, empty, status,

@@ -20,7 +20,7 @@ import collections
 import numpy as np
 import torch
 
-from . import _lib
+from . import _args, _lib
 from . import augment as _aug
 from .pairgen import invert_rigid
 
@@ -28,7 +28,7 @@ ONLY_OFF_MASK, MASK_INV = 1, 2
 BAD_INDEX, BAD_DRAWS, BAD_OFFSETS = 1, 2, 4
 CONCAT_MAX_GROUPS = 8
 SITES = ("cand", "masked", "background", "blind", "across_a", "across_b")
-CAM_FLOATS = 50
+CAM_FLOATS = _args.CAM_FLOATS
 SINGLE_OBJECT_WITHIN_SCENE, SINGLE_OBJECT_ACROSS_SCENE, DIFFERENT_OBJECT, MULTI_OBJECT, SYNTHETIC_MULTI_OBJECT = 0, 1, 2, 3, 4
 
 SampleOptions = collections.namedtuple(
@@ -73,34 +73,9 @@ def options_from_config(training_config):
                          bool(t["use_image_b_mask_inv"]), int(t["cross_scene_num_samples"]), bool(t["domain_randomize"]))
 
 
-def _mask(m, n, h, w, what):
-    if tuple(m.shape) != (n, h, w):
-        raise ValueError("%s must be [%d, %d, %d], got %s" % (what, n, h, w, tuple(m.shape)))
-    return (m if m.dtype == torch.uint8 else m.to(torch.uint8)).contiguous()
-
-
-def _depth(d, n, h, w, what):
-    if tuple(d.shape) != (n, h, w) or d.element_size() != 2 or d.is_floating_point():
-        raise ValueError("%s must be 16-bit integer [%d, %d, %d] millimetres, got %s %s" % (what, n, h, w, d.dtype,
-                                                                                            tuple(d.shape)))
-    return d.contiguous()
-
-
-def _f32(a):
-    return np.asarray(a, dtype=np.float64).astype(np.float32)
-
-
 def _cameras(K, pose_a, pose_b, n, dev):
     """[n, CAM_FLOATS] fp32 (K, K^-1, pose a, pose b^-1) on ``dev`` in one copy, as pairgen.find_correspondences builds them."""
-    if K is None:
-        from dense_correspondence.correspondence_tools.correspondence_finder import get_default_K_matrix
-        K = get_default_K_matrix()
-    K = np.asarray(K.cpu() if torch.is_tensor(K) else K, dtype=np.float64)
-    Ks = np.broadcast_to(K, (n, 3, 3)) if K.shape == (3, 3) else K
-    if Ks.shape != (n, 3, 3):
-        raise ValueError("K must be [3, 3] or [%d, 3, 3], got %s" % (n, K.shape))
-    rows = [np.concatenate([_f32(k).reshape(-1), _f32(np.linalg.inv(k)).reshape(-1)]) for k in Ks]
-    rows = torch.from_numpy(np.stack(rows))
+    rows = torch.from_numpy(_args.camera_k_rows(K, n)[1])
     poses = []
     for p, what in ((pose_a, "pose_a"), (pose_b, "pose_b")):
         if tuple(p.shape) != (n, 4, 4):
@@ -109,7 +84,7 @@ def _cameras(K, pose_a, pose_b, n, dev):
     if all(not torch.is_tensor(p) or p.device.type == "cpu" for p in poses):
         pa = np.asarray(poses[0].numpy() if torch.is_tensor(poses[0]) else poses[0], dtype=np.float64)
         pb = np.asarray(poses[1].numpy() if torch.is_tensor(poses[1]) else poses[1], dtype=np.float64)
-        t = np.concatenate([rows.numpy(), _f32(pa).reshape(n, 16), np.stack([_f32(invert_rigid(x)).reshape(16) for x in pb])],
+        t = np.concatenate([rows.numpy(), _args.f32(pa).reshape(n, 16), np.stack([_args.f32(invert_rigid(x)).reshape(16) for x in pb])],
                            axis=1)
         host = torch.from_numpy(np.ascontiguousarray(t))
         if dev.type == "cuda":
@@ -156,17 +131,13 @@ def pack_draws(draws, n, dev):
     return rand.to(dev), torch.tensor(offs, dtype=torch.int64).to(dev)
 
 
-def _random(n, dev, generator, draws, seeds):
+def random_source(n, dev, generator, draws, seeds):
+    """-> (seeds, rand, rand_offsets): the replay streams of ``draws`` (pack_draws) and no seeds, or per-pair seeds (the
+    caller's, or drawn with ``generator``) and no streams."""
     if draws is not None:
         rand, roff = pack_draws(draws, n, dev)
         return None, rand, roff
-    if seeds is None:
-        seeds = draw_seeds(n, dev, generator)
-    else:
-        seeds = torch.as_tensor(seeds).to(device=dev, dtype=torch.int64).contiguous().view(-1)
-        if seeds.numel() != n:
-            raise ValueError("seeds must hold one int64 per pair (%d)" % n)
-    return seeds, None, None
+    return _args.seeds_for(n, dev, generator, seeds), None, None
 
 
 def _params(aug_params, n, dev, generator, domain_randomize, flip):
@@ -178,20 +149,30 @@ def _params(aug_params, n, dev, generator, domain_randomize, flip):
     return p
 
 
-def _outputs(n, cap, dev):
+def _open(mask_a, mask_b):
+    """What every builder starts from: the batch's sizes and device (mask a's) and both masks as the kernels take them."""
+    n, h, w = int(mask_a.shape[0]), int(mask_a.shape[1]), int(mask_a.shape[2])
+    return n, h, w, mask_a.device, _args.mask(mask_a, n, h, w, "mask_a"), _args.mask(mask_b, n, h, w, "mask_b")
+
+
+def _outputs(n, cap, dev, workspace_bytes):
+    """idx_a, idx_b [cap], offsets [4n + 1], empty [n], type [n], status [1] and the workspace"""
     return (torch.empty(max(cap, 1), dtype=torch.int64, device=dev)[:cap], torch.empty(max(cap, 1), dtype=torch.int64,
                                                                                        device=dev)[:cap],
             torch.empty(4 * n + 1, dtype=torch.int64, device=dev), torch.empty(n, dtype=torch.bool, device=dev),
-            torch.empty(n, dtype=torch.int32, device=dev), torch.empty(1, dtype=torch.int32, device=dev))
+            torch.empty(n, dtype=torch.int32, device=dev), torch.empty(1, dtype=torch.int32, device=dev),
+            torch.empty(int(workspace_bytes), dtype=torch.uint8, device=dev))
 
 
-def _images(rgb_a, rgb_b, mask_a, mask_b, params, mean, std):
-    if rgb_a is None and rgb_b is None:
-        return None, None, None, None
-    if rgb_a is None or rgb_b is None:
+def _batch(outs, sd, params, max_list_len, max_pair_len, rgb_a=None, rgb_b=None, mask_a=None, mask_b=None, mean=None, std=None):
+    """The SampleBatch of a builder's outputs and, with RGB, the augmentation launch that writes the network's inputs."""
+    ia = ib = mka = mkb = None
+    if (rgb_a is None) != (rgb_b is None):
         raise ValueError("rgb_a and rgb_b go together")
-    out = _aug.augment_images(rgb_a, mask_a, params, rgb_b=rgb_b, mask_b=mask_b, mean=mean, std=std)
-    return out["input_a"], out["input_b"], out["mask_a"], out["mask_b"]
+    if rgb_a is not None:
+        out = _aug.augment_images(rgb_a, mask_a, params, rgb_b=rgb_b, mask_b=mask_b, mean=mean, std=std)
+        ia, ib, mka, mkb = out["input_a"], out["input_b"], out["mask_a"], out["mask_b"]
+    return SampleBatch(ia, ib, *outs[:6], sd, params, mka, mkb, max_list_len, max_pair_len)
 
 
 def build_within_scene_samples(depth_a, depth_b, mask_a, mask_b, pose_a, pose_b, K=None, rgb_a=None, rgb_b=None, *,
@@ -211,36 +192,26 @@ def build_within_scene_samples(depth_a, depth_b, mask_a, mask_b, pose_a, pose_b,
 
     -> SampleBatch.  Launches: the sample chain (about ten small kernels) and, with RGB, one augmentation launch; no host
     synchronization."""
-    n, h, w = int(mask_a.shape[0]), int(mask_a.shape[1]), int(mask_a.shape[2])
-    dev = mask_a.device
     lib = _lib.get()
-    da, db = _depth(depth_a, n, h, w, "depth_a"), _depth(depth_b, n, h, w, "depth_b")
-    ma, mb = _mask(mask_a, n, h, w, "mask_a"), _mask(mask_b, n, h, w, "mask_b")
+    n, h, w, dev, ma, mb = _open(mask_a, mask_b)
+    da, db = _args.depth(depth_a, n, h, w, "depth_a"), _args.depth(depth_b, n, h, w, "depth_b")
     A, k1, k2 = int(num_matching_attempts), int(num_masked_non_matches_per_match), int(num_background_non_matches_per_match)
     if A < 1 or k1 < 1 or k2 < 1:
         raise ValueError("num_matching_attempts and the non-matches per match must be >= 1")
     params = _params(aug_params, n, dev, generator, domain_randomize, flip)
-    sd, rand, roff = _random(n, dev, generator, draws, seeds)
-    if cameras is None:
-        cams = _cameras(K, pose_a, pose_b, n, dev)
-    else:
-        cams = cameras
-        if tuple(cams.shape) != (n, CAM_FLOATS) or cams.dtype != torch.float32 or not cams.is_contiguous():
-            raise ValueError("cameras must be contiguous float32 [%d, %d], got %s %s" % (n, CAM_FLOATS, cams.dtype,
-                                                                                      tuple(cams.shape)))
+    sd, rand, roff = random_source(n, dev, generator, draws, seeds)
+    cams = _cameras(K, pose_a, pose_b, n, dev) if cameras is None else _args.camera_rows(cameras, n, "cameras", as_given=True)
     _lib.require_device(da, db, ma, mb, cams, params, sd, rand, roff)
     cap = n * (A * (1 + k1 + k2) + h * w)
-    idx_a, idx_b, offsets, empty, typ, status = _outputs(n, cap, dev)
-    ws = torch.empty(int(lib.dcn_sample_workspace(n, h, w, A, A)), dtype=torch.uint8, device=dev)
+    outs = _outputs(n, cap, dev, lib.dcn_sample_workspace(n, h, w, A, A))
+    idx_a, idx_b, offsets, empty, typ, status, ws = outs
     flags = (ONLY_OFF_MASK if sample_matches_only_off_mask else 0) | (MASK_INV if use_image_b_mask_inv else 0)
     P = _lib.ptr
     rc = lib.dcn_within_scene_samples(n, h, w, P(da), P(db), P(ma), P(mb), P(cams), A, k1, k2, flags, P(params), P(sd),
                                       P(rand), P(roff), int(data_type), P(idx_a), P(idx_b), cap, P(offsets), P(empty),
                                       P(typ), P(status), P(ws), _lib.stream_ptr())
     _lib.check(rc, "dcn_within_scene_samples")
-    ia, ib, mka, mkb = _images(rgb_a, rgb_b, ma, mb, params, mean, std)
-    return SampleBatch(ia, ib, idx_a, idx_b, offsets, empty, typ, status, sd, params, mka, mkb, max(A, A * k1, A * k2, h * w),
-                       cap // n)
+    return _batch(outs, sd, params, max(A, A * k1, A * k2, h * w), cap // n, rgb_a, rgb_b, ma, mb, mean, std)
 
 
 def build_across_scene_samples(mask_a, mask_b, rgb_a=None, rgb_b=None, *, num_samples, domain_randomize=False, flip=True,
@@ -249,25 +220,22 @@ def build_across_scene_samples(mask_a, mask_b, rgb_a=None, rgb_b=None, *, num_sa
     """B across-scene / different-object samples on the device (get_across_scene_data): ``num_samples`` pixels of each mask,
     rotated by the pair's records, as the blind lists; a pair with an empty mask is empty.  Arguments as
     build_within_scene_samples; -> SampleBatch."""
-    n, h, w = int(mask_a.shape[0]), int(mask_a.shape[1]), int(mask_a.shape[2])
-    dev = mask_a.device
     lib = _lib.get()
-    ma, mb = _mask(mask_a, n, h, w, "mask_a"), _mask(mask_b, n, h, w, "mask_b")
+    n, h, w, dev, ma, mb = _open(mask_a, mask_b)
     ns = int(num_samples)
     if ns < 1:
         raise ValueError("num_samples must be >= 1")
     params = _params(aug_params, n, dev, generator, domain_randomize, flip)
-    sd, rand, roff = _random(n, dev, generator, draws, seeds)
+    sd, rand, roff = random_source(n, dev, generator, draws, seeds)
     _lib.require_device(ma, mb, params, sd, rand, roff)
     cap = n * ns
-    idx_a, idx_b, offsets, empty, typ, status = _outputs(n, cap, dev)
-    ws = torch.empty(int(lib.dcn_sample_workspace(n, h, w, 0, 0)), dtype=torch.uint8, device=dev)
+    outs = _outputs(n, cap, dev, lib.dcn_sample_workspace(n, h, w, 0, 0))
+    idx_a, idx_b, offsets, empty, typ, status, ws = outs
     P = _lib.ptr
     rc = lib.dcn_across_scene_samples(n, h, w, P(ma), P(mb), ns, P(params), P(sd), P(rand), P(roff), int(data_type), P(idx_a),
                                       P(idx_b), cap, P(offsets), P(empty), P(typ), P(status), P(ws), _lib.stream_ptr())
     _lib.check(rc, "dcn_across_scene_samples")
-    ia, ib, mka, mkb = _images(rgb_a, rgb_b, ma, mb, params, mean, std)
-    return SampleBatch(ia, ib, idx_a, idx_b, offsets, empty, typ, status, sd, params, mka, mkb, ns, ns)
+    return _batch(outs, sd, params, ns, ns, rgb_a, rgb_b, ma, mb, mean, std)
 
 
 def complete_samples(uv_a, uv_b, offsets, mask_a, mask_b, *, num_masked_non_matches_per_match,
@@ -278,39 +246,32 @@ def complete_samples(uv_a, uv_b, offsets, mask_a, mask_b, *, num_masked_non_matc
     ([B + 1] tensor or sequence; a -1 capacity tail after offsets[B] is ignored); mask_a, mask_b: 0/1 [B, H, W] of the
     frames the lists index.  ``aug_params`` (optional): rotation records to apply to lists and masks first.  A pair without
     matches is empty.  -> SampleBatch (no images)."""
-    n, h, w = int(mask_a.shape[0]), int(mask_a.shape[1]), int(mask_a.shape[2])
-    dev = mask_a.device
     lib = _lib.get()
-    ma, mb = _mask(mask_a, n, h, w, "mask_a"), _mask(mask_b, n, h, w, "mask_b")
+    n, h, w, dev, ma, mb = _open(mask_a, mask_b)
     ua, va = uv_a[0].contiguous(), uv_a[1].contiguous()
     ub, vb = uv_b[0].contiguous(), uv_b[1].contiguous()
     if ua.dtype != torch.int64 or va.dtype != torch.int64 or ub.dtype != vb.dtype or len({int(x.numel()) for x in
                                                                                           (ua, va, ub, vb)}) != 1:
         raise ValueError("uv_a must be int64, uv_b int64 or float32, all four lists of one length")
-    uv_b_dtype = _aug._uv_dtype(ub)
-    if not torch.is_tensor(offsets):
-        offsets = torch.tensor([int(o) for o in offsets], dtype=torch.int64)
-    if offsets.numel() != n + 1:
-        raise ValueError("offsets must have B + 1 = %d entries, got %d" % (n + 1, offsets.numel()))
-    off = offsets.to(device=dev, dtype=torch.int64, non_blocking=True).contiguous().view(-1)
+    uv_b_dtype = _args.uv_dtype(ub)
+    off = _args.offsets(offsets, n, dev)
     k1, k2 = int(num_masked_non_matches_per_match), int(num_background_non_matches_per_match)
     if k1 < 1 or k2 < 1:
         raise ValueError("the non-matches per match must be >= 1")
     params = None if aug_params is None else _params(aug_params, n, dev, None, False, True)
-    sd, rand, roff = _random(n, dev, generator, draws, seeds)
+    sd, rand, roff = random_source(n, dev, generator, draws, seeds)
     _lib.require_device(ua, va, ub, vb, off, ma, mb, params, sd, rand, roff)
     count = int(ua.numel())
     cap = count * (1 + k1 + k2) + n * h * w
-    idx_a, idx_b, offsets_out, empty, typ, status = _outputs(n, cap, dev)
-    ws = torch.empty(int(lib.dcn_sample_workspace(n, h, w, 0, count)), dtype=torch.uint8, device=dev)
+    outs = _outputs(n, cap, dev, lib.dcn_sample_workspace(n, h, w, 0, count))
+    idx_a, idx_b, offsets_out, empty, typ, status, ws = outs
     P = _lib.ptr
     rc = lib.dcn_complete_samples(n, h, w, P(ua), P(va), P(ub), P(vb), uv_b_dtype, P(off), count, P(ma), P(mb), k1, k2,
                                   MASK_INV if use_image_b_mask_inv else 0, P(params), P(sd), P(rand), P(roff), int(data_type),
                                   P(idx_a), P(idx_b), cap, P(offsets_out), P(empty), P(typ), P(status), P(ws),
                                   _lib.stream_ptr())
     _lib.check(rc, "dcn_complete_samples")
-    return SampleBatch(None, None, idx_a, idx_b, offsets_out, empty, typ, status, sd, params, None, None,
-                       max(count, count * k1, count * k2, h * w), count * (1 + k1 + k2) + h * w)
+    return _batch(outs, sd, params, max(count, count * k1, count * k2, h * w), count * (1 + k1 + k2) + h * w)
 
 
 def _cat(parts):
