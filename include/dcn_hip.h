@@ -928,6 +928,44 @@ int dcn_match_statistics_pairs(int p, int h, int w, int d, const float* res_a, c
                                int max_pair_rows, double* columns, uint8_t* is_valid, int32_t* pred_uv, int32_t* closer,
                                int32_t* row_pair, int32_t* mask_pixels, int32_t* status, void* workspace, void* stream);
 
+/* -----------------------------------------------------------------------------------------------------
+ * 11c. Across-object evaluation -- replaces, for device-resident masks and descriptor images, what
+ *     single_across_object_image_pair_quantitative_analysis (evaluation.py:784-859) runs per image pair of two DIFFERENT
+ *     objects: random_sample_from_masked_image(mask_a, q) (correspondence_finder.py:68-90) and, per sampled pixel,
+ *     compute_descriptor_match_statistics_no_ground_truth (:977-1003), i.e. find_best_match over the whole of image b
+ *     (dense_correspondence_network.py:488-550, no mask), for ALL pairs in one call each.  P pairs of [h][w] images.
+ *
+ *     Queries: mask_a uint8 [P][hw], res_a float [P][hw][d].  n_p = mask a's non-zero pixels.  Pair p gets q rows when
+ *     n_p >= q, and none otherwise: n_p == 0 is the reference's empty list, 0 < n_p < q raises
+ *     DCN_ACROSS_TOO_FEW_MASK_PIXELS (random.sample raises "Sample larger than population" there).  Row j of the pair is the
+ *     non-zero pixel number r_j in row-major order (numpy's nonzero() order), with r_j = sample_order[p][j] (replay: int32
+ *     [P][q], the reference's rand_inds; a rank outside [0, n_p) reads 0, and it or a rank repeated within the pair raises
+ *     DCN_EVAL_BAD_DRAWS), or, with sample_order == NULL, the rank in place j when the n_p ranks are ordered by a hash of
+ *     (order_seeds[p], rank), ties by rank -- a uniform random order, its first q entries (the order of 11a).
+ *     Outputs: rows [offsets[p], offsets[p+1]) of u_a, v_a (int64) and queries (float [.][d], res_a at the pixel), each with
+ *     P * q rows, -1 / 0 from offsets[P] on; offsets int64 [P + 1]; mask_pixels int32 [P]; status int32 [1] (written).
+ *     1 <= P <= 1024, 1 <= q <= 1024, 1 <= d <= 64, h * w < 2^31.
+ *
+ *     Search: for every row of pair p the first minimum, in flat v * w + u order, of the fp32 distance
+ *     sqrt(sum_c (res_b[p][pixel][c] - queries[row][c])^2) (summed with fma in channel order, as section 4) over ALL pixels of
+ *     res_b float [P][hw][d]; queries float [max_rows][d]; offsets int64 [P + 1] on the device, checked as in 11b
+ *     (DCN_EVAL_BAD_OFFSETS; max_pair_rows <= 1024 rows per pair).  res_b is read ONCE whatever the number of rows.
+ *       norm_diff float [max_rows] (norm_diff_descriptor_best_match); best_uv int32 [2][max_rows] (u, v); row_pair int32
+ *       [max_rows]; status int32 [1] (written).  Rows from offsets[P] on: NaN, -1, -1.
+ *     Partial minima are combined as 64-bit integers (distance bits, pixel): bit-identical from run to run.  A NaN distance
+ *     never wins.  No host synchronisation in either.
+ * ----------------------------------------------------------------------------------------------------- */
+#define DCN_ACROSS_TOO_FEW_MASK_PIXELS 16   /* status: a mask a with fewer non-zero pixels than samples asked (the pair has no rows) */
+size_t dcn_across_object_queries_workspace(int p, int h, int w);
+int dcn_across_object_queries(int p, int h, int w, int d, const uint8_t* mask_a, const float* res_a, int q,
+                              const int32_t* sample_order, const int64_t* order_seeds, int64_t* u_a, int64_t* v_a,
+                              float* queries, int64_t* offsets, int32_t* mask_pixels, int32_t* status, void* workspace,
+                              void* stream);
+size_t dcn_best_match_pairs_workspace(int64_t max_rows);
+int dcn_best_match_pairs(int p, int h, int w, int d, const float* res_b, const float* queries, const int64_t* offsets,
+                         int64_t max_rows, int max_pair_rows, float* norm_diff, int32_t* best_uv, int32_t* row_pair,
+                         int32_t* status, void* workspace, void* stream);
+
 /* =====================================================================================================
  * 12. Descriptor statistics of a dataset -- replaces, for device-resident descriptor images, the per-image half and the
  *     running update of DenseCorrespondenceEvaluation.compute_descriptor_statistics_on_dataset

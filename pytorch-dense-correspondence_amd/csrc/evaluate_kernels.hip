@@ -13,8 +13,12 @@
 //   pair_rows_kernel    one work-item per row: unpacks the keys and finishes the columns; the depth / 3D half (:1102-1135,
 //                       :1148-1164) in float64 from the fp32 camera row.
 #include "dcn_common.h"
+#include "eval_rows.h"
 
 namespace {
+
+using dcn::check_offsets_kernel;
+using dcn::pair_rows;
 
 constexpr int kMT = 256;    // work-items (pixels) per workgroup
 constexpr int kQT = 32;     // queries staged in LDS at a time
@@ -55,37 +59,6 @@ __device__ __forceinline__ int clip_round(float x, int size, int& bad) {
         return 0;
     }
     return r >= (float)size ? size - 1 : (int)r;
-}
-
-// offsets must increase from >= 0 to <= max_rows over ALL pairs (no pair's rows may overlap another's): one violation
-// anywhere raises DCN_EVAL_BAD_OFFSETS and sets *flag, and then every pair is empty.
-__global__ void __launch_bounds__(256) check_offsets_kernel(const int64_t* __restrict__ offsets, int np, int64_t max_rows,
-                                                            int32_t* flag, int32_t* status) {
-    const int p = blockIdx.x * 256 + threadIdx.x;
-    if (p >= np) return;
-    const int64_t lo = offsets[p], hi = offsets[p + 1];
-    if (lo < 0 || hi < lo || hi > max_rows) {
-        atomicOr(flag, 1);
-        atomicOr(status, DCN_EVAL_BAD_OFFSETS);
-    }
-}
-
-// Rows [lo, lo + n) of pair p; none when the offsets failed check_offsets_kernel; a list longer than max_pair_rows is cut
-// (DCN_EVAL_BAD_OFFSETS)
-__device__ __forceinline__ void pair_rows(const int64_t* offsets, const int32_t* offsets_bad, int p, int64_t max_rows,
-                                          int max_pair_rows, int64_t& lo, int& n, int& bad) {
-    lo = offsets[p];
-    int64_t hi = offsets[p + 1];
-    if (*offsets_bad || lo < 0 || hi < lo || hi > max_rows) {
-        bad |= DCN_EVAL_BAD_OFFSETS;
-        lo = 0;
-        hi = 0;
-    }
-    if (hi - lo > max_pair_rows) {
-        bad |= DCN_EVAL_BAD_OFFSETS;
-        hi = lo + max_pair_rows;
-    }
-    n = (int)(hi - lo);
 }
 
 template <int DT>

@@ -21,6 +21,7 @@
 // Random numbers: uniform on torch.rand's 24-bit grid from a counter-based hash of (pair seed, site, index), or replayed from
 // the caller's streams (include/dcn_hip.h section 9).
 #include "dcn_common.h"
+#include "hashed_order.h"
 #include "pairgen_project.h"
 
 namespace {
@@ -45,14 +46,7 @@ struct Draws {
     int n;
 };
 
-__device__ __forceinline__ uint32_t mix32(uint32_t x) {
-    x ^= x >> 16;
-    x *= 0x7feb352dU;
-    x ^= x >> 15;
-    x *= 0x846ca68bU;
-    x ^= x >> 16;
-    return x;
-}
+using dcn::mix32;
 
 // Uniform number `idx` of stream `site` of pair p: the hash of (seed, site, idx) on torch.rand's grid (k / 2^24), or the
 // caller's value; a replay stream that is too short reads 0 and raises DCN_SAMPLE_BAD_DRAWS.
@@ -688,10 +682,7 @@ __global__ void __launch_bounds__(1024) eval_offsets_kernel(EvalArgs a) {
     }
 }
 
-__device__ __forceinline__ uint32_t order_key(uint64_t s, uint32_t i) {
-    const uint32_t k0 = mix32((uint32_t)s ^ 0x2545F491U);
-    return mix32(mix32(i ^ k0) ^ (mix32((uint32_t)(s >> 32) ^ k0) + 0x9E3779B9U));
-}
+using dcn::order_key;
 
 // grid (ceil(attempts / 256), n): work-item e of pair p.  Replay: e < k is output row e, survivor order[p][e].  Seeded: e <
 // total is survivor e, whose rank among the total hashed keys (ties by index) is its row when below k.  Every work-item with

@@ -216,6 +216,11 @@ SYMBOLS = {
     "dcn_match_statistics_pairs_workspace": (c_size_t, [c_int64]),
     "dcn_match_statistics_pairs": (c_int, [c_int, c_int, c_int, c_int] + [c_void_p] * 11 + [c_int64, c_int]
                                    + [c_void_p] * 9),
+    "dcn_across_object_queries_workspace": (c_size_t, [c_int, c_int, c_int]),
+    "dcn_across_object_queries": (c_int, [c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_int] + [c_void_p] * 10),
+    "dcn_best_match_pairs_workspace": (c_size_t, [c_int64]),
+    "dcn_best_match_pairs": (c_int, [c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int64, c_int]
+                             + [c_void_p] * 6),
     "dcn_descriptor_statistics_workspace": (c_size_t, [c_int, c_int, c_int, c_int]),
     "dcn_descriptor_statistics": (c_int, [c_int, c_int, c_int, c_int] + [c_void_p] * 6),
     "dcn_descriptor_statistics_combine": (c_int, [c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p]),
