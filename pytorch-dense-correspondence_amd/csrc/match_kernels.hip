@@ -4,11 +4,14 @@
 // evaluation.py:932-950).  Here ALL queries of an image are answered by one pass over the descriptor image:
 // HBM-bound, algorithmic traffic = HW * D * 4 bytes once (+ Q * HW * 4 when the distance images are requested).
 // One work-item per pixel keeps its descriptor in registers and loops over the queries (LDS broadcast reads);
-// per query: wave64 shuffle min-reduction of the packed key (dist2 bits << 32 | pixel index), across the workgroup's
+// per query: wave64 shuffle min-reduction of the packed key (norm bits << 32 | pixel index), across the workgroup's
 // wavefronts through LDS, then at most one 64-bit atomicMin per WORKGROUP -- and only when the key beats the value
 // currently in memory (a plain load first: thousands of workgroups target the same Q words, and after the first few
 // almost every key loses; without the look the kernel is serialised on those atomics: 12 us -> 1 us per query).
-// The key order makes ties resolve to the smallest index, exactly like np.argmin.
+// The key holds the NORM, sqrtf(dist2), not dist2: the square root maps about two neighbouring squared distances onto one
+// norm, and np.argmin sees the norms -- of two pixels with one norm it returns the first, whichever has the smaller squared
+// distance.  So the key order makes ties resolve to the smallest index, exactly like np.argmin, and the returned pixel is
+// the first argmin of the norm_diffs image this call writes (match_stats_kernel and acrossobj_kernels.hip key the same way).
 #include "dcn_common.h"
 
 namespace {
@@ -42,8 +45,9 @@ best_match_kernel(const float* __restrict__ res, int64_t hw, int d_rt, const flo
             for (int k = 0; k < (DT > 0 ? DT : kMaxD); ++k) {
                 if (k < D) { const float t = v[k] - sq[q * D + k]; d2 = fmaf(t, t, d2); }
             }
-            if (norm_diffs && in) norm_diffs[(int64_t)(q0 + q) * hw + pix] = sqrtf(d2);
-            unsigned long long key = cand ? (((unsigned long long)__float_as_uint(d2)) << 32) | (unsigned long long)(unsigned)pix
+            const float dd = sqrtf(d2);
+            if (norm_diffs && in) norm_diffs[(int64_t)(q0 + q) * hw + pix] = dd;
+            unsigned long long key = cand ? (((unsigned long long)__float_as_uint(dd)) << 32) | (unsigned long long)(unsigned)pix
                                           : ~0ull;
 #pragma unroll
             for (int off = 32; off > 0; off >>= 1) {
@@ -71,7 +75,7 @@ best_match_unpack_kernel(const unsigned long long* __restrict__ best, int nq, in
     const unsigned long long k = best[q];
     if (k == ~0ull) { idx[q] = -1; dist[q] = INFINITY; return; }  // empty mask
     idx[q] = (int64_t)(k & 0xffffffffull);
-    dist[q] = sqrtf(__uint_as_float((unsigned)(k >> 32)));
+    dist[q] = __uint_as_float((unsigned)(k >> 32));   // (already the norm, not its square)
 }
 
 // ------------------------------------------------------------------------------------------------ match statistics
@@ -81,7 +85,7 @@ best_match_unpack_kernel(const unsigned long long* __restrict__ best, int nq, in
 //   t = ||queries[q] - res_b[gt[q]]||, the number of pixels with d < t (image / mask) and the sum of their pixel distances to
 //   gt[q] (for "average_l2_distance_for_false_positives").  d = sqrt(sum_k (res_b - query)^2) in fp32.
 struct MatchStats {
-    unsigned long long* best;     // [2][Q] packed (d2 bits << 32 | pixel): image, masked (masked: d2 -> bits of (d + 1e6) outside)
+    unsigned long long* best;     // [2][Q] packed (norm bits << 32 | pixel): image, masked (masked: bits of (d + 1e6) outside)
     int* count;                   // [2][Q]
     float* dist_sum;              // [2][Q]
     float* gt_d;                  // [Q]
@@ -152,7 +156,7 @@ match_stats_kernel(const float* __restrict__ res, int64_t hw, int w, int d_rt, c
             }
         }
         __syncthreads();
-        if ((int)threadIdx.x < 2 * qn) {
+        if ((int)threadIdx.x < (mask ? 2 : 1) * qn) {        // (no mask: match_stats_unpack_kernel copies the image half)
             const int which = threadIdx.x / qn, q = threadIdx.x - which * qn;
             unsigned long long key = skey[which][q][0];
             int n = scnt[which][q][0];
@@ -173,12 +177,19 @@ match_stats_kernel(const float* __restrict__ res, int64_t hw, int w, int d_rt, c
     }
 }
 
+// masked == 0 (no mask given): the masked half IS the image half, count and dist_sum included -- copied here, so that the two
+// halves are equal bit for bit (two float-atomic sums of the same terms differ in their last bits with the order of the adds).
 __global__ void __launch_bounds__(256)
-match_stats_unpack_kernel(const unsigned long long* __restrict__ best, int nq, int64_t* __restrict__ idx,
-                          float* __restrict__ dist) {
+match_stats_unpack_kernel(const unsigned long long* __restrict__ best, int nq, int masked, int64_t* __restrict__ idx,
+                          float* __restrict__ dist, int* __restrict__ count, float* __restrict__ dist_sum) {
     const int q = blockIdx.x * 256 + threadIdx.x;   // over 2 * nq
     if (q >= 2 * nq) return;
-    const unsigned long long k = best[q];
+    const bool copy = !masked && q >= nq;
+    const unsigned long long k = best[copy ? q - nq : q];
+    if (copy) {
+        count[q] = count[q - nq];
+        dist_sum[q] = dist_sum[q - nq];
+    }
     idx[q] = (int64_t)(k & 0xffffffffull);
     dist[q] = __uint_as_float((unsigned)(k >> 32));   // (already the norm, not its square)
 }
@@ -188,7 +199,7 @@ match_stats_unpack_kernel(const unsigned long long* __restrict__ best, int nq, i
 extern "C" size_t dcn_match_statistics_workspace(int q) { return (size_t)(q > 0 ? q : 1) * 2 * sizeof(unsigned long long); }
 
 // best_idx / best_dist: [2][Q] (image, masked); count: [2][Q] int32; dist_sum: [2][Q]; gt_dist: [Q].  mask may be NULL
-// (then the "masked" half equals the image half).
+// (then the "masked" half is a copy of the image half, bit for bit).
 extern "C" int dcn_match_statistics(const float* res, int64_t hw, int w, int d, const float* queries, const int64_t* gt_idx,
                                     int q, const unsigned char* mask, int64_t* best_idx, float* best_dist, int32_t* count,
                                     float* dist_sum, float* gt_dist, void* workspace, void* stream) {
@@ -214,7 +225,7 @@ extern "C" int dcn_match_statistics(const float* res, int64_t hw, int w, int d, 
     }
 #undef DCN_MS
     hipLaunchKernelGGL(match_stats_unpack_kernel, dim3(dcn::ceil_div(2 * q, 256)), dim3(256), 0, st,
-                       (const unsigned long long*)o.best, q, best_idx, best_dist);
+                       (const unsigned long long*)o.best, q, mask ? 1 : 0, best_idx, best_dist, count, dist_sum);
     return dcn::check_launch();
 }
 

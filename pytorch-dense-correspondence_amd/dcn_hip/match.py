@@ -6,7 +6,10 @@ from . import _lib
 
 def find_best_matches(res, queries, mask=None, return_norm_diffs=False):
     """res: [H, W, D] (or [HW, D]) descriptor image, queries: [Q, D] -> (best_flat_idx int64 [Q], best_dist [Q],
-    norm_diffs [Q, H, W] or None).  Same arithmetic as dense_correspondence_network.py:541-547 for every query."""
+    norm_diffs [Q, H, W] or None).  Same arithmetic as dense_correspondence_network.py:541-547 for every query.
+    mask: optional [H, W] (or [HW]); only its non-zero pixels are candidates, the first of equal minima wins.  Where every
+    candidate's distance is inf (an overflowing descriptor image) the result is still the first pixel OF THE MASK, with
+    distance inf; an empty mask gives index -1 and inf."""
     lib = _lib.get()
     shape = res.shape
     d = int(shape[-1])
@@ -33,7 +36,7 @@ def match_statistics(res_b, queries, gt_idx, mask=None):
     (u + W*v) of the ground-truth match in image b, mask: optional [H, W] (non-zero = on the object).
     One pass over res_b (evaluation.py:1046-1100 for every query) -> dict of device tensors, "image" / "masked" pairs as
     [2, Q]: best_idx, best_dist, count (pixels closer than the ground truth), dist_sum (their pixel distance to it), and
-    gt_dist [Q]."""
+    gt_dist [Q].  Without a mask the "masked" row of each is a copy of the "image" row, bit for bit."""
     lib = _lib.get()
     h, w, d = (int(s) for s in res_b.shape)
     res2 = res_b.reshape(-1, d).contiguous().float()
