@@ -966,6 +966,43 @@ int dcn_best_match_pairs(int p, int h, int w, int d, const float* res_b, const f
                          int64_t max_rows, int max_pair_rows, float* norm_diff, int32_t* best_uv, int32_t* row_pair,
                          int32_t* status, void* workspace, void* stream);
 
+/* -----------------------------------------------------------------------------------------------------
+ * 11d. Cross-scene evaluation -- replaces, for a frame store and device-resident descriptor images, what
+ *     single_cross_scene_image_pair_quantitative_analysis (evaluation.py:610-781) runs per human-labelled match: the
+ *     reprojection of the labelled pixel into other views of its scene (batch_find_pixel_correspondences(..., uv_a=<one
+ *     pixel>), :721, :756) and compute_descriptor_match_statistics (:1045-1175) of every resulting row.
+ *
+ *     Reprojection: v requests over the store itself (section 10's tables; nothing is gathered), requests int32 [v][4] =
+ *     (src frame, u, v, dst frame).  kcam float [18]: K then K^-1, row-major fp32 (section 10's scene_cams layout) -- given
+ *     explicitly because the reference passes no K to this search, which therefore runs with get_default_K_matrix() whatever
+ *     the scene's K is.  Arithmetic: section 9's reprojection test (fp32, the reference's evaluation order, the 3 mm occlusion
+ *     margin, an exactly-zero coordinate pruned) with pose src as fp32 and pose dst^-1 as section 10's camera rows carry it
+ *     (float64 R^T and -(R^T t) summed left to right, then fp32): a request gets the answer 11a gives that candidate.
+ *       found uint8 [v]; u2, v2 float [v] (the projection, as the reference's search returns it; 0 when image src has no depth
+ *       there); uv int32 [2][v] (clip_pixel_to_image_size_and_round of the projection; -1 when not found); status int32 [1]
+ *       (written): DCN_EVAL_BAD_FRAME for a frame index or a pixel outside the store -- that request is not found and
+ *       nothing is read out of range.  One work-item per request.  v >= 1.
+ *
+ *     Statistics: 11b for GROUPS of rows that search one image.  Group g searches res_b[g] (float [G][hw][d]) with mask_b[g]
+ *     (uint8 [G][hw]) and depth_b[g] (uint16 [G][hw]); its rows are [offsets[g], offsets[g+1]) (offsets int64 [G + 1] on the
+ *     device, checked as in 11b; max_group_rows bounds one group's rows, which may exceed the kernel's query tile).  Every row
+ *     carries its own query descriptor queries[r][d], query pixel u_a, v_a (int64), the depth there depth_q[r] (uint16
+ *     millimetres), ground truth u_b, v_b (float, rounded and clipped as in 11b), camera row cams[r][DCN_SAMPLE_CAM_FLOATS]
+ *     and keep[r] (uint8).  A row with keep == 0 costs no search, none of its other inputs is looked at, and it comes out like
+ *     a row past offsets[G].  Outputs and arithmetic are 11b's (the same device functions): columns, is_valid, pred_uv, closer,
+ *     row_pair (the row's GROUP, or -1), mask_pixels int32 [G], status int32 [1] (written).  64-bit integer atomics only:
+ *     bit-identical from run to run.  No host synchronisation.  1 <= G <= 65535, 1 <= d <= 64, h * w < 2^31.
+ * ----------------------------------------------------------------------------------------------------- */
+int dcn_reproject_pixels(int v, const struct dcn_frame_store* store, const float* kcam, const int32_t* requests,
+                         uint8_t* found, float* u2, float* v2, int32_t* uv, int32_t* status, void* stream);
+size_t dcn_match_statistics_groups_workspace(int64_t max_rows);
+int dcn_match_statistics_groups(int g, int h, int w, int d, const float* res_b, const uint8_t* mask_b, const uint16_t* depth_b,
+                                const float* queries, const int64_t* u_a, const int64_t* v_a, const uint16_t* depth_q,
+                                const float* u_b, const float* v_b, const float* cams, const uint8_t* keep,
+                                const int64_t* offsets, int64_t max_rows, int max_group_rows, double* columns,
+                                uint8_t* is_valid, int32_t* pred_uv, int32_t* closer, int32_t* row_pair, int32_t* mask_pixels,
+                                int32_t* status, void* workspace, void* stream);
+
 /* =====================================================================================================
  * 12. Descriptor statistics of a dataset -- replaces, for device-resident descriptor images, the per-image half and the
  *     running update of DenseCorrespondenceEvaluation.compute_descriptor_statistics_on_dataset

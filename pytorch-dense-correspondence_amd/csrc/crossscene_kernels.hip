@@ -1,0 +1,333 @@
+// Cross-scene evaluation on the frame store (include/dcn_hip.h section 11d): what
+// single_cross_scene_image_pair_quantitative_analysis (evaluation.py:610-781) runs per human-labelled match and per extra view.
+//
+//   reproject_kernel    one work-item per request (src frame, u, v, dst frame) over the store itself: the labelled pixel
+//                       reprojected into another view, batch_find_pixel_correspondences(..., uv_a=<one pixel>).  pairgen_project.h's
+//                       project_candidate on camera entries made as frame_kernels.hip's camera_row makes them (pose a in fp32;
+//                       pose b^-1 from float64, left-to-right sums), so a request gets the answer dcn_eval_matches would give
+//                       that candidate.  A few dozen bytes per request.
+//   group_stats_kernel  grid (pixel tiles, groups).  pair_stats_kernel's scheme (evaluate_kernels.hip; the per-pixel loop IS
+//                       eval_stats.h's), but group g's rows all search the ONE image res_b[g], and each row brings its own query
+//                       descriptor: image b of an annotated pair is searched by its labelled rows and by every a-view's row
+//                       without being copied once per row.  A row with keep == 0 is passed over.
+//                       HBM traffic: G * HW * D * 4 bytes of res_b once, G * HW mask bytes, and R * D query floats per
+//                       workgroup from L2.
+//   group_rows_kernel   one work-item per row: eval_stats.h's finish_row with the row's own depth and camera row.
+#include "dcn_common.h"
+#include "eval_rows.h"
+#include "eval_stats.h"
+#include "pairgen_project.h"
+
+namespace {
+
+using dcn::check_offsets_kernel;
+using dcn::clip_round;
+using dcn::pair_rows;
+
+constexpr int kMT = dcn::kEvalMT;
+constexpr int kQT = dcn::kEvalQT;
+constexpr int kMaxD = dcn::kEvalMaxD;
+constexpr int kCam = DCN_SAMPLE_CAM_FLOATS;
+
+// float64 products and sums that the compiler may not contract (the rigid inverse, as frame_kernels.hip's camera_row)
+#if defined(DCN_HOSTEMU_BUILD)
+inline double mul_rn(double a, double b) { return a * b; }
+inline double add_rn(double a, double b) { return a + b; }
+#else
+__device__ __forceinline__ double mul_rn(double a, double b) { return __dmul_rn(a, b); }
+__device__ __forceinline__ double add_rn(double a, double b) { return __dadd_rn(a, b); }
+#endif
+
+struct Reproject {
+    const uint16_t* depth;         // the store's [F][hw]
+    const double* poses;           // the store's [F][16]
+    const float* kcam;             // [18]: K, K^-1
+    const int32_t* requests;       // [V][4]: src frame, u, v, dst frame
+    uint8_t* found;                // [V]
+    float* u2;                     // [V] the projection
+    float* v2;
+    int32_t* uv;                   // [2][V] clip_pixel_to_image_size_and_round of it (-1 when not found)
+    int32_t* status;
+    int64_t num_frames, hw;
+    int v, h, w;
+};
+
+__global__ void __launch_bounds__(256) reproject_kernel(Reproject a) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= a.v) return;
+    const int64_t fa = a.requests[4 * (size_t)i], fb = a.requests[4 * (size_t)i + 3];
+    const int64_t u = a.requests[4 * (size_t)i + 1], v = a.requests[4 * (size_t)i + 2];
+    unsigned char ok = 0;
+    float pu = 0.f, pv = 0.f;
+    if (fa < 0 || fa >= a.num_frames || fb < 0 || fb >= a.num_frames || u < 0 || u >= a.w || v < 0 || v >= a.h) {
+        atomicOr(a.status, DCN_EVAL_BAD_FRAME);
+    } else {
+        const double* pa = a.poses + fa * 16;
+        const double* pb = a.poses + fb * 16;
+        float Ta[12], Tb[12];
+#pragma unroll
+        for (int e = 0; e < 12; ++e) Ta[e] = (float)pa[e];
+#pragma unroll
+        for (int r = 0; r < 3; ++r) {
+#pragma unroll
+            for (int c = 0; c < 3; ++c) Tb[4 * r + c] = (float)pb[4 * c + r];          // (R^T)_rc
+            double s = mul_rn(pb[r], pb[3]);                                           // -(R^T t)_r, summed left to right
+            s = add_rn(s, mul_rn(pb[4 + r], pb[7]));
+            s = add_rn(s, mul_rn(pb[8 + r], pb[11]));
+            Tb[4 * r + 3] = (float)(-s);
+        }
+        ok = dcn::project_candidate(a.depth + fa * a.hw, a.depth + fb * a.hw, a.h, a.w, a.kcam, a.kcam + 9, Ta, Tb, u, v, pu, pv);
+    }
+    int bad = 0;
+    a.found[i] = ok;
+    a.u2[i] = pu;
+    a.v2[i] = pv;
+    a.uv[i] = ok ? clip_round(pu, a.w, bad) : -1;
+    a.uv[(size_t)a.v + i] = ok ? clip_round(pv, a.h, bad) : -1;
+}
+
+struct GroupStats {
+    const float* res_b;            // [G][hw][D]
+    const uint8_t* mask_b;         // [G][hw]
+    const float* queries;          // [rows][D]
+    const int64_t* u_a;            // [rows] the query pixel (only checked here)
+    const int64_t* v_a;
+    const float* u_b;              // [rows] ground truth in the group's image
+    const float* v_b;
+    const uint8_t* keep;           // [rows]
+    const int64_t* offsets;        // [G + 1]
+    const int32_t* offsets_bad;    // [1] set by check_offsets_kernel
+    unsigned long long* best;      // [2][R] packed (norm bits << 32 | pixel): image, masked
+    int32_t* count;                // [2][R]
+    unsigned long long* dist_sum;  // [2][R] sum of pixel distances in units of 2^-20 pixel
+    float* gt_d;                   // [R]
+    int32_t* mask_pixels;          // [G]
+    int32_t* status;
+    int64_t hw, max_rows;
+    int w, h, d, max_group_rows;
+};
+
+template <int DT>
+__global__ void __launch_bounds__(kMT) group_stats_kernel(GroupStats a) {
+    __shared__ dcn::EvalTile s;
+    const int D = DT > 0 ? DT : a.d;
+    const int g = blockIdx.y, w = a.w;
+    const int64_t hw = a.hw;
+    const int64_t pix = (int64_t)blockIdx.x * kMT + threadIdx.x;
+    const bool in = pix < hw;
+    const bool onm = in && a.mask_b[(size_t)g * hw + pix] != 0;
+    {   // num_pixels_in_masked_image (evaluation.py:1085)
+        const int n = dcn::wave_sum<int>(onm ? 1 : 0);
+        if ((threadIdx.x & 63) == 0 && n) atomicAdd(a.mask_pixels + g, n);
+    }
+    int bad = 0;
+    int64_t lo;
+    int nq;
+    pair_rows(a.offsets, a.offsets_bad, g, a.max_rows, a.max_group_rows, lo, nq, bad);
+    if (bad && blockIdx.x == 0 && threadIdx.x == 0) atomicOr(a.status, bad);
+    if (nq == 0) return;               // (uniform per workgroup)
+    const float* res = a.res_b + (size_t)g * hw * D;
+    const int pu = in ? (int)(pix % w) : 0, pv = in ? (int)(pix / w) : 0;
+    float v[DT > 0 ? DT : kMaxD];
+#pragma unroll
+    for (int k = 0; k < (DT > 0 ? DT : kMaxD); ++k) v[k] = (in && k < D) ? res[pix * D + k] : 0.f;
+    for (int q0 = 0; q0 < nq; q0 += kQT) {
+        const int qn = min(kQT, nq - q0);
+        __syncthreads();
+        if ((int)threadIdx.x < qn) {
+            const int64_t r = lo + q0 + threadIdx.x;
+            const bool kept = a.keep[r] != 0;
+            int rb = 0, gu = 0, gv = 0;
+            if (kept) {                // (what a row left out carries is never looked at)
+                if (a.u_a[r] < 0 || a.u_a[r] >= w || a.v_a[r] < 0 || a.v_a[r] >= a.h) rb |= DCN_EVAL_BAD_INDEX;
+                gu = clip_round(a.u_b[r], w, rb);
+                gv = clip_round(a.v_b[r], a.h, rb);
+            }
+            s.skip[threadIdx.x] = kept ? 0 : 1;
+            s.sgu[threadIdx.x] = gu;
+            s.sgv[threadIdx.x] = gv;
+            if (rb && blockIdx.x == 0) atomicOr(a.status, rb);
+        }
+        for (int i = threadIdx.x; i < qn * D; i += kMT) s.sq[i] = a.queries[(lo + q0) * D + i];
+        __syncthreads();
+        dcn::stats_ground_truth(s, res, D, w, qn, blockIdx.x == 0, a.gt_d + lo + q0);
+        __syncthreads();
+        dcn::stats_scan<DT, true>(s, v, D, qn, in, onm, pix, pu, pv, a.best, a.count, a.dist_sum, a.max_rows, lo + q0);
+    }
+}
+
+struct GroupRows {
+    const uint16_t* depth_b;       // [G][hw]
+    const uint16_t* depth_q;       // [rows] depth at the query pixel, millimetres
+    const float* cams;             // [rows][kCam]: K, K^-1, pose a, pose b^-1
+    const int64_t* u_a;
+    const int64_t* v_a;
+    const float* u_b;
+    const float* v_b;
+    const uint8_t* keep;
+    const int64_t* offsets;
+    const int32_t* offsets_bad;
+    const unsigned long long* best;
+    const int32_t* count;          // [2][R] (the `closer` output)
+    const unsigned long long* dist_sum;
+    const float* gt_d;
+    const int32_t* mask_pixels;
+    dcn::EvalRowOut out;
+    int64_t hw;
+    int w, h, ng, max_group_rows;
+};
+
+__global__ void __launch_bounds__(256) group_rows_kernel(GroupRows a) {
+    const int64_t r = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    const int64_t R = a.out.max_rows;
+    if (r >= R) return;
+    int lo = 0, hi = a.ng;
+    while (lo < hi) {                                       // first g with offsets[g + 1] > r
+        const int mid = (lo + hi) >> 1;
+        if (a.offsets[mid + 1] > r) hi = mid;
+        else lo = mid + 1;
+    }
+    const int g = lo;
+    int bad = 0;
+    int64_t first = 0;
+    int n = 0;
+    if (g < a.ng) pair_rows(a.offsets, a.offsets_bad, g, R, a.max_group_rows, first, n, bad);
+    const bool mine = g < a.ng && r >= first && r < first + n && a.keep[r] != 0;
+    const unsigned long long k0 = mine ? a.best[r] : ~0ull, k1 = mine ? a.best[R + r] : ~0ull;
+    if (!mine || k0 == ~0ull || k1 == ~0ull) {              // past the last row, cut off a bad list, left out, or no key written
+        dcn::empty_row(a.out, r);
+        return;
+    }
+    const int w = a.w, h = a.h;
+    int ua = (int)a.u_a[r], va = (int)a.v_a[r];
+    if (a.u_a[r] < 0 || a.u_a[r] >= w || a.v_a[r] < 0 || a.v_a[r] >= h) ua = va = 0;
+    const int gu = clip_round(a.u_b[r], w, bad), gv = clip_round(a.v_b[r], h, bad);
+    dcn::finish_row(a.out, r, g, k0, k1, ua, va, a.depth_q[r], gu, gv, a.depth_b + (size_t)g * a.hw, a.cams + (size_t)r * kCam,
+                    a.gt_d[r], a.count[r], a.count[R + r], a.dist_sum[r], a.dist_sum[R + r], a.mask_pixels[g], a.hw, w);
+}
+
+inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
+
+}  // namespace
+
+extern "C" int dcn_reproject_pixels(int v, const dcn_frame_store* store, const float* kcam, const int32_t* requests,
+                                    uint8_t* found, float* u2, float* v2, int32_t* uv, int32_t* status, void* stream) {
+    if (v < 1 || !store || store->num_frames < 1 || store->h < 1 || store->w < 1 || !store->depth || !store->poses || !kcam ||
+        !requests || !found || !u2 || !v2 || !uv || !status)
+        return DCN_E_INVALID;
+    hipStream_t st = (hipStream_t)stream;
+    const int rc = dcn::fill_bytes_async(status, 0, sizeof(int32_t), st);
+    if (rc != DCN_OK) return rc;
+    Reproject a;
+    a.depth = store->depth;
+    a.poses = store->poses;
+    a.kcam = kcam;
+    a.requests = requests;
+    a.found = found;
+    a.u2 = u2;
+    a.v2 = v2;
+    a.uv = uv;
+    a.status = status;
+    a.num_frames = store->num_frames;
+    a.hw = (int64_t)store->h * store->w;
+    a.v = v;
+    a.h = store->h;
+    a.w = store->w;
+    hipLaunchKernelGGL(reproject_kernel, dim3(dcn::ceil_div(v, 256)), dim3(256), 0, st, a);
+    return dcn::check_launch();
+}
+
+// best [2][R] u64 | dist_sum [2][R] u64 | gt_d [R] float | offsets_bad int32
+extern "C" size_t dcn_match_statistics_groups_workspace(int64_t max_rows) {
+    const size_t r = (size_t)(max_rows > 0 ? max_rows : 1);
+    return 2 * align256(r * 2 * sizeof(unsigned long long)) + align256(r * sizeof(float)) + 256;
+}
+
+extern "C" int dcn_match_statistics_groups(int g, int h, int w, int d, const float* res_b, const uint8_t* mask_b,
+                                           const uint16_t* depth_b, const float* queries, const int64_t* u_a, const int64_t* v_a,
+                                           const uint16_t* depth_q, const float* u_b, const float* v_b, const float* cams,
+                                           const uint8_t* keep, const int64_t* offsets, int64_t max_rows, int max_group_rows,
+                                           double* columns, uint8_t* is_valid, int32_t* pred_uv, int32_t* closer,
+                                           int32_t* row_pair, int32_t* mask_pixels, int32_t* status, void* workspace,
+                                           void* stream) {
+    const int64_t hw = (int64_t)h * w;
+    if (g < 1 || g > 65535 || h < 1 || w < 1 || hw >= ((int64_t)1 << 31) || d < 1 || d > kMaxD || !res_b || !mask_b || !depth_b ||
+        !queries || !u_a || !v_a || !depth_q || !u_b || !v_b || !cams || !keep || !offsets || max_rows < 1 ||
+        max_group_rows < 1 || !columns || !is_valid || !pred_uv || !closer || !row_pair || !mask_pixels || !status || !workspace)
+        return DCN_E_INVALID;
+    hipStream_t st = (hipStream_t)stream;
+    char* ws = (char*)workspace;
+    const size_t R = (size_t)max_rows;
+    GroupStats a;
+    a.best = (unsigned long long*)ws;
+    a.dist_sum = (unsigned long long*)(ws + align256(R * 2 * sizeof(unsigned long long)));
+    a.gt_d = (float*)((char*)a.dist_sum + align256(R * 2 * sizeof(unsigned long long)));
+    a.count = closer;
+    int32_t* flag = (int32_t*)((char*)a.gt_d + align256(R * sizeof(float)));
+    a.offsets_bad = flag;
+    int rc = dcn::fill_bytes_async(a.best, 0xFF, R * 2 * sizeof(unsigned long long), st);
+    if (rc == DCN_OK) rc = dcn::fill_bytes_async(closer, 0, R * 2 * sizeof(int32_t), st);
+    if (rc == DCN_OK) rc = dcn::fill_bytes_async(a.dist_sum, 0, R * 2 * sizeof(unsigned long long), st);
+    if (rc == DCN_OK) rc = dcn::fill_bytes_async(a.gt_d, 0, align256(R * sizeof(float)), st);
+    if (rc == DCN_OK) rc = dcn::fill_bytes_async(mask_pixels, 0, (size_t)g * sizeof(int32_t), st);
+    if (rc == DCN_OK) rc = dcn::fill_bytes_async(status, 0, sizeof(int32_t), st);
+    if (rc == DCN_OK) rc = dcn::fill_bytes_async(flag, 0, sizeof(int32_t), st);
+    if (rc != DCN_OK) return rc;
+    hipLaunchKernelGGL(check_offsets_kernel, dim3(dcn::ceil_div(g, 256)), dim3(256), 0, st, offsets, g, max_rows, flag, status);
+    a.res_b = res_b;
+    a.mask_b = mask_b;
+    a.queries = queries;
+    a.u_a = u_a;
+    a.v_a = v_a;
+    a.u_b = u_b;
+    a.v_b = v_b;
+    a.keep = keep;
+    a.offsets = offsets;
+    a.mask_pixels = mask_pixels;
+    a.status = status;
+    a.hw = hw;
+    a.max_rows = max_rows;
+    a.w = w;
+    a.h = h;
+    a.d = d;
+    a.max_group_rows = max_group_rows;
+    const dim3 grid((unsigned)dcn::ceil_div64(hw, kMT), (unsigned)g), block(kMT);
+#define DCN_GS(DT) hipLaunchKernelGGL((group_stats_kernel<DT>), grid, block, 0, st, a)
+    switch (d) {
+        case 3: DCN_GS(3); break;
+        case 4: DCN_GS(4); break;
+        case 8: DCN_GS(8); break;
+        case 16: DCN_GS(16); break;
+        case 32: DCN_GS(32); break;
+        default: DCN_GS(0); break;
+    }
+#undef DCN_GS
+    GroupRows b;
+    b.depth_b = depth_b;
+    b.depth_q = depth_q;
+    b.cams = cams;
+    b.u_a = u_a;
+    b.v_a = v_a;
+    b.u_b = u_b;
+    b.v_b = v_b;
+    b.keep = keep;
+    b.offsets = offsets;
+    b.offsets_bad = flag;
+    b.best = a.best;
+    b.count = closer;
+    b.dist_sum = a.dist_sum;
+    b.gt_d = a.gt_d;
+    b.mask_pixels = mask_pixels;
+    b.out.col = columns;
+    b.out.is_valid = is_valid;
+    b.out.pred_uv = pred_uv;
+    b.out.row_pair = row_pair;
+    b.out.max_rows = max_rows;
+    b.hw = hw;
+    b.w = w;
+    b.h = h;
+    b.ng = g;
+    b.max_group_rows = max_group_rows;
+    hipLaunchKernelGGL(group_rows_kernel, dim3((unsigned)dcn::ceil_div64(max_rows, 256)), dim3(256), 0, st, b);
+    return dcn::check_launch();
+}

@@ -1,0 +1,247 @@
+// The search and the row finishing of the match statistics, shared by the pair-wise entry (evaluate_kernels.hip: a query's
+// descriptor, depth and camera row come from image a of its pair) and the grouped entry (crossscene_kernels.hip: every row
+// carries its own).  One text for both, so the two entries compute the same bits for the same rows.
+//
+//   stats_ground_truth / stats_scan   one query tile of a statistics kernel (kEvalMT pixels x up to kEvalQT queries staged in
+//                                     an EvalTile): the fma chain over channels, sqrtf, + 1e6f off the mask, packed-key minima
+//                                     (norm bits << 32 | pixel: ties go to the smallest index, as np.argmin), wave64 shuffle
+//                                     reductions, then per workgroup and query at most one 64-bit atomicMin -- after a plain
+//                                     load: thousands of workgroups target the same few words and almost every key loses.
+//   finish_row / empty_row            one row of the table from its keys, counts and sums; the depth / 3D half
+//                                     (evaluation.py:1102-1135, :1148-1164) in float64 from the row's fp32 camera row.
+#pragma once
+#include "dcn_common.h"
+
+namespace dcn {
+
+constexpr int kEvalMT = 256;    // work-items (pixels) per workgroup
+constexpr int kEvalQT = 32;     // queries staged in LDS at a time
+constexpr int kEvalMaxD = 64;
+constexpr double kEvalSumScale = 1048576.0;   // pixel distances are summed as integers of 2^-20 pixel: the sum does not depend on the order
+
+// clip_pixel_to_image_size_and_round (evaluation.py:604-607): min(int(round(x)), size - 1), Python 2's round (half away from
+// zero: roundf).  NaN or a negative result reads 0 and sets `bad`.
+__device__ __forceinline__ int clip_round(float x, int size, int& bad) {
+    if (!(x == x)) {
+        bad |= DCN_EVAL_BAD_INDEX;
+        return 0;
+    }
+    const float r = roundf(x);
+    if (r < 0.f) {
+        bad |= DCN_EVAL_BAD_INDEX;
+        return 0;
+    }
+    return r >= (float)size ? size - 1 : (int)r;
+}
+
+// The LDS of one query tile: the kernel declares it __shared__, fills sq / sgu / sgv (and skip), and synchronizes
+struct EvalTile {
+    float sq[kEvalQT * kEvalMaxD];     // query descriptors, [query][D]
+    float st[kEvalQT];                 // squared ground-truth distance
+    int sgu[kEvalQT], sgv[kEvalQT];    // ground-truth pixel in the searched image
+    unsigned long long skey[2][kEvalQT][kEvalMT / 64];
+    int scnt[2][kEvalQT][kEvalMT / 64];
+    unsigned long long ssum[2][kEvalQT][kEvalMT / 64];
+    unsigned char skip[kEvalQT];       // (grouped entry) the row takes no part in the search
+};
+
+// Work-items < qn: the squared distance between query q and the searched image at q's ground truth -> s.st; the first
+// workgroup of the image also stores its root at gt_d[q].  Needs s.sq, s.sgu, s.sgv; the caller synchronizes afterwards.
+__device__ __forceinline__ void stats_ground_truth(EvalTile& s, const float* __restrict__ res, int D, int w, int qn,
+                                                   bool first_workgroup, float* gt_d) {
+    if ((int)threadIdx.x < qn) {
+        const int64_t g = (int64_t)s.sgv[threadIdx.x] * w + s.sgu[threadIdx.x];
+        float t2 = 0.f;
+        for (int k = 0; k < D; ++k) {
+            const float t = res[g * D + k] - s.sq[threadIdx.x * D + k];
+            t2 = fmaf(t, t, t2);
+        }
+        s.st[threadIdx.x] = t2;
+        if (first_workgroup) gt_d[threadIdx.x] = sqrtf(t2);
+    }
+}
+
+// This work-item's pixel (descriptor v, flat index pix = pv * w + pu, `in` the image, `onm` the mask) against the tile's qn
+// queries; results go to rows row0 .. row0 + qn - 1 of best / count / dist_sum ([2][max_rows]: image, masked).  SKIP: queries
+// with s.skip set are passed over (uniform per workgroup) and nothing is written for them.  Needs s.st; ends after the
+// atomics, the caller synchronizes before it refills the tile.
+template <int DT, bool SKIP>
+__device__ __forceinline__ void stats_scan(EvalTile& s, const float (&v)[DT > 0 ? DT : kEvalMaxD], int D, int qn, bool in,
+                                           bool onm, int64_t pix, int pu, int pv, unsigned long long* best, int32_t* count,
+                                           unsigned long long* dist_sum, int64_t max_rows, int64_t row0) {
+    const int wv = threadIdx.x >> 6;
+    for (int q = 0; q < qn; ++q) {
+        if (SKIP && __builtin_amdgcn_readfirstlane((int)s.skip[q])) continue;   // (one scalar branch per query)
+        float d2 = 0.f;
+#pragma unroll
+        for (int k = 0; k < (DT > 0 ? DT : kEvalMaxD); ++k) {
+            if (k < D) { const float t = v[k] - s.sq[q * D + k]; d2 = fmaf(t, t, d2); }
+        }
+        const float dd = sqrtf(d2), tt = sqrtf(s.st[q]);
+        const float dm = onm ? dd : dd + 1e6f;                         // masked_norm_diffs
+        unsigned long long k0 = in ? (((unsigned long long)__float_as_uint(dd)) << 32) | (unsigned)pix : ~0ull;
+        unsigned long long k1 = in ? (((unsigned long long)__float_as_uint(dm)) << 32) | (unsigned)pix : ~0ull;
+        const bool c0 = in && dd < tt, c1 = in && dm < tt;
+        const float du = (float)(pu - s.sgu[q]), dv = (float)(pv - s.sgv[q]);
+        const float pd = sqrtf(du * du + dv * dv);
+        int n0 = c0 ? 1 : 0, n1 = c1 ? 1 : 0;
+        const unsigned long long pf = (unsigned long long)((double)pd * kEvalSumScale + 0.5);
+        unsigned long long s0 = c0 ? pf : 0ull, s1 = c1 ? pf : 0ull;
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) {
+            const unsigned long long x = __shfl_down(k0, off, 64), y = __shfl_down(k1, off, 64);
+            k0 = x < k0 ? x : k0;
+            k1 = y < k1 ? y : k1;
+            n0 += __shfl_down(n0, off, 64);
+            n1 += __shfl_down(n1, off, 64);
+            s0 += __shfl_down(s0, off, 64);
+            s1 += __shfl_down(s1, off, 64);
+        }
+        if ((threadIdx.x & 63) == 0) {
+            s.skey[0][q][wv] = k0; s.skey[1][q][wv] = k1;
+            s.scnt[0][q][wv] = n0; s.scnt[1][q][wv] = n1;
+            s.ssum[0][q][wv] = s0; s.ssum[1][q][wv] = s1;
+        }
+    }
+    __syncthreads();
+    if ((int)threadIdx.x < 2 * qn) {
+        const int which = threadIdx.x / qn, q = threadIdx.x - which * qn;
+        if (!(SKIP && s.skip[q])) {
+            unsigned long long key = s.skey[which][q][0];
+            int n = s.scnt[which][q][0];
+            unsigned long long sum = s.ssum[which][q][0];
+#pragma unroll
+            for (int x = 1; x < kEvalMT / 64; ++x) {
+                key = s.skey[which][q][x] < key ? s.skey[which][q][x] : key;
+                n += s.scnt[which][q][x];
+                sum += s.ssum[which][q][x];
+            }
+            const int64_t o = (int64_t)which * max_rows + row0 + q;
+            unsigned long long* slot = best + o;
+            if (key != ~0ull && key < __atomic_load_n(slot, __ATOMIC_RELAXED)) atomicMin(slot, key);
+            if (n) {
+                atomicAdd(count + o, n);
+                atomicAdd(dist_sum + o, sum);
+            }
+        }
+    }
+}
+
+// The table's outputs, every row dimension max_rows
+struct EvalRowOut {
+    double* col;                   // [DCN_EVAL_COLUMNS][R]
+    uint8_t* is_valid;             // [2][R]
+    int32_t* pred_uv;              // [4][R]
+    int32_t* row_pair;             // [R]
+    int64_t max_rows;
+};
+
+struct EvalVec3 {
+    double x, y, z;
+};
+
+// compute_3d_position (evaluation.py:1181-1200): pose * (z * K^-1 * (u, v, 1)); Ki = K^-1 (row-major), R / t the pose's rows
+__device__ __forceinline__ EvalVec3 eval_position(const double* Ki, const double* R, const double* t, int u, int v, double z) {
+    const double cx = z * (Ki[0] * u + Ki[1] * v + Ki[2]);
+    const double cy = z * (Ki[3] * u + Ki[4] * v + Ki[5]);
+    const double cz = z * (Ki[6] * u + Ki[7] * v + Ki[8]);
+    EvalVec3 o;
+    o.x = R[0] * cx + R[1] * cy + R[2] * cz + t[0];
+    o.y = R[3] * cx + R[4] * cy + R[5] * cz + t[1];
+    o.z = R[6] * cx + R[7] * cy + R[8] * cz + t[2];
+    return o;
+}
+
+__device__ __forceinline__ double eval_norm3(const EvalVec3& a, const EvalVec3& b) {
+    const double x = a.x - b.x, y = a.y - b.y, z = a.z - b.z;
+    return sqrt(x * x + y * y + z * z);
+}
+
+__device__ __forceinline__ bool eval_depth_valid(double d) { return d > 0.0 && d < 10.0; }   // is_depth_valid (:961-972)
+
+// A row past the last one, cut off a bad list, left out, or without a key: NaN columns, zero flags, -1
+__device__ __forceinline__ void empty_row(const EvalRowOut& o, int64_t r) {
+    const int64_t R = o.max_rows;
+    const double nan = __builtin_nan("");
+#pragma unroll
+    for (int c = 0; c < DCN_EVAL_COLUMNS; ++c) o.col[(int64_t)c * R + r] = nan;
+    o.is_valid[r] = 0;
+    o.is_valid[R + r] = 0;
+#pragma unroll
+    for (int c = 0; c < 4; ++c) o.pred_uv[(int64_t)c * R + r] = -1;
+    o.row_pair[r] = -1;
+}
+
+// Row r of pair / group p from its keys k0, k1 (image, masked), counts c0, c1 and distance sums s0, s1: query pixel (ua, va)
+// whose depth is da_mm millimetres, ground truth (gu, gv) in the searched image, whose depth plane is db and whose mask has nm
+// pixels; cam: the row's K, K^-1, pose a, pose b^-1 (fp32).
+__device__ __forceinline__ void finish_row(const EvalRowOut& o, int64_t r, int p, unsigned long long k0, unsigned long long k1,
+                                           int ua, int va, uint16_t da_mm, int gu, int gv, const uint16_t* __restrict__ db,
+                                           const float* __restrict__ cam, float gt_d, int c0, int c1, unsigned long long s0,
+                                           unsigned long long s1, int nm, int64_t hw, int w) {
+    const int64_t R = o.max_rows;
+    const double nan = __builtin_nan("");
+    const int i0 = (int)(unsigned)(k0 & 0xffffffffull), i1 = (int)(unsigned)(k1 & 0xffffffffull);
+    const int u0 = i0 % w, v0 = i0 / w, u1 = i1 % w, v1 = i1 / w;
+    o.row_pair[r] = p;
+    o.pred_uv[r] = u0;
+    o.pred_uv[R + r] = v0;
+    o.pred_uv[2 * R + r] = u1;
+    o.pred_uv[3 * R + r] = v1;
+    o.col[(int64_t)DCN_EVAL_COL_NORM_DIFF_DESCRIPTOR_GROUND_TRUTH * R + r] = (double)gt_d;
+    o.col[(int64_t)DCN_EVAL_COL_NORM_DIFF_DESCRIPTOR * R + r] = (double)__uint_as_float((unsigned)(k0 >> 32));
+    o.col[(int64_t)DCN_EVAL_COL_NORM_DIFF_DESCRIPTOR_MASKED * R + r] = (double)__uint_as_float((unsigned)(k1 >> 32));
+    {
+        const double du = (double)(gu - u0), dv = (double)(gv - v0), dum = (double)(gu - u1), dvm = (double)(gv - v1);
+        o.col[(int64_t)DCN_EVAL_COL_PIXEL_MATCH_ERROR_L2 * R + r] = sqrt(du * du + dv * dv);
+        o.col[(int64_t)DCN_EVAL_COL_PIXEL_MATCH_ERROR_L2_MASKED * R + r] = sqrt(dum * dum + dvm * dvm);
+        o.col[(int64_t)DCN_EVAL_COL_PIXEL_MATCH_ERROR_L1 * R + r] = fabs(du) + fabs(dv);
+    }
+    o.col[(int64_t)DCN_EVAL_COL_FRACTION_CLOSER * R + r] = (double)c0 * 1.0 / (double)hw;
+    o.col[(int64_t)DCN_EVAL_COL_FRACTION_CLOSER_MASKED * R + r] = nm > 0 ? (double)c1 * 1.0 / (double)nm : nan;
+    o.col[(int64_t)DCN_EVAL_COL_AVERAGE_L2_FALSE_POSITIVES * R + r] = c0 ? (double)s0 / kEvalSumScale / (double)c0 : 0.0;
+    o.col[(int64_t)DCN_EVAL_COL_AVERAGE_L2_FALSE_POSITIVES_MASKED * R + r] = c1 ? (double)s1 / kEvalSumScale / (double)c1 : 0.0;
+    // ---- depth / 3D half, float64
+    const double za = (double)da_mm / 1000.0, zb = (double)db[(int64_t)gv * w + gu] / 1000.0;
+    const double z0 = (double)db[i0] / 1000.0, z1 = (double)db[i1] / 1000.0;
+    const bool valid0 = eval_depth_valid(z0), valid1 = eval_depth_valid(z1), validb = eval_depth_valid(zb);
+    o.is_valid[r] = valid0 ? 1 : 0;
+    o.is_valid[R + r] = valid1 ? 1 : 0;
+    double K[9], Ki[9], Ra[9], ta[3], Rb[9], tb[3];
+#pragma unroll
+    for (int i = 0; i < 9; ++i) K[i] = (double)cam[i];
+    {   // inverse of K by its adjugate
+        const double c00 = K[4] * K[8] - K[5] * K[7], c01 = K[5] * K[6] - K[3] * K[8], c02 = K[3] * K[7] - K[4] * K[6];
+        const double det = K[0] * c00 + K[1] * c01 + K[2] * c02;
+        Ki[0] = c00 / det;
+        Ki[1] = (K[2] * K[7] - K[1] * K[8]) / det;
+        Ki[2] = (K[1] * K[5] - K[2] * K[4]) / det;
+        Ki[3] = c01 / det;
+        Ki[4] = (K[0] * K[8] - K[2] * K[6]) / det;
+        Ki[5] = (K[2] * K[3] - K[0] * K[5]) / det;
+        Ki[6] = c02 / det;
+        Ki[7] = (K[1] * K[6] - K[0] * K[7]) / det;
+        Ki[8] = (K[0] * K[4] - K[1] * K[3]) / det;
+    }
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+#pragma unroll
+        for (int j = 0; j < 3; ++j) {
+            Ra[3 * i + j] = (double)cam[18 + 4 * i + j];
+            Rb[3 * i + j] = (double)cam[34 + 4 * j + i];                  // (R_b^-1)^T
+        }
+        ta[i] = (double)cam[18 + 4 * i + 3];
+    }
+    {
+        const double t0 = (double)cam[34 + 3], t1 = (double)cam[34 + 7], t2 = (double)cam[34 + 11];
+#pragma unroll
+        for (int i = 0; i < 3; ++i) tb[i] = -(Rb[3 * i] * t0 + Rb[3 * i + 1] * t1 + Rb[3 * i + 2] * t2);
+    }
+    const EvalVec3 pa = eval_position(Ki, Ra, ta, ua, va, za), pb = eval_position(Ki, Rb, tb, gu, gv, zb);
+    const EvalVec3 p0 = eval_position(Ki, Rb, tb, u0, v0, z0), p1 = eval_position(Ki, Rb, tb, u1, v1, z1);
+    o.col[(int64_t)DCN_EVAL_COL_NORM_DIFF_GROUND_TRUTH_3D * R + r] = validb ? eval_norm3(pb, pa) : nan;
+    o.col[(int64_t)DCN_EVAL_COL_NORM_DIFF_PRED_3D * R + r] = (validb && valid0) ? eval_norm3(pb, p0) : nan;
+    o.col[(int64_t)DCN_EVAL_COL_NORM_DIFF_PRED_3D_MASKED * R + r] = (validb && valid1) ? eval_norm3(pb, p1) : nan;
+}
+
+}  // namespace dcn

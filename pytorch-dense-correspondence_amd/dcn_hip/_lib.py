@@ -221,6 +221,10 @@ SYMBOLS = {
     "dcn_best_match_pairs_workspace": (c_size_t, [c_int64]),
     "dcn_best_match_pairs": (c_int, [c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int64, c_int]
                              + [c_void_p] * 6),
+    "dcn_reproject_pixels": (c_int, [c_int, ctypes.POINTER(FrameStoreDesc)] + [c_void_p] * 8),
+    "dcn_match_statistics_groups_workspace": (c_size_t, [c_int64]),
+    "dcn_match_statistics_groups": (c_int, [c_int, c_int, c_int, c_int] + [c_void_p] * 12 + [c_int64, c_int]
+                                    + [c_void_p] * 9),
     "dcn_descriptor_statistics_workspace": (c_size_t, [c_int, c_int, c_int, c_int]),
     "dcn_descriptor_statistics": (c_int, [c_int, c_int, c_int, c_int] + [c_void_p] * 6),
     "dcn_descriptor_statistics_combine": (c_int, [c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p]),

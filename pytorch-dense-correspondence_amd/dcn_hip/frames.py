@@ -75,7 +75,8 @@ class FrameStore(object):
         self.depth = depth if depth.dtype == torch.int16 else depth.view(torch.int16)
         self.poses = torch.as_tensor(poses, dtype=torch.float64).to(dev).reshape(F, 16).contiguous()
         # host copy of the frame translations, float64 [F, 3] (evaluate.choose_pairs)
-        self.translations_host = self.poses.view(F, 4, 4)[:, :3, 3].cpu().numpy().copy()
+        self.poses_host = self.poses.view(F, 4, 4).cpu().numpy().copy()     # float64 [F, 4, 4] (evaluate.choose_cross_scene_views)
+        self.translations_host = self.poses_host[:, :3, 3].copy()
         Ks, cams = _args.camera_k_rows(K, S)                 # (K | K^-1 per scene: the first 18 floats of a camera row)
         self.K = np.array(Ks, dtype=np.float64)
         self.scene_cams = torch.from_numpy(np.ascontiguousarray(cams, dtype=np.float32)).to(dev)
