@@ -47,7 +47,9 @@ const char* dcn_version(void);
 /* The DCN_* environment overrides -- the full list with their meaning is the header comment of csrc/dcn_tuning.h:
  * DCN_CONV_MODE, DCN_BACKWARD_OVERLAP, DCN_GEMM_TILE_M, DCN_STEM8, DCN_GEMM_SK, DCN_GEMM_SK_MIN_GAIN,
  * DCN_GEMM_UNI, DCN_GEMM_SK_FIXUP, DCN_BN_BWD_FUSED, DCN_DEFER_RESIDUAL_ADD, DCN_WGRAD_TILE, DCN_WGRAD_DEEP, DCN_WGRAD_ROLES,
- * DCN_WGRAD_SPLITS, DCN_GEMM_HL, DCN_HL_MIN_K, DCN_GEMM_HL_ROWS, DCN_WGRAD_HL, DCN_HL_PRODUCERS, DCN_HL_ONLY_MID, DCN_STEM_POOL_FUSED, DCN_BN_REVERSE, DCN_BN_NT, DCN_BN_REDUCE_WIDE, DCN_WSPLIT_OVERLAP -- are read ONCE, at the first call that needs them -- never on the
+ * DCN_WGRAD_SPLITS, DCN_GEMM_HL, DCN_HL_MIN_K, DCN_GEMM_HL_ROWS, DCN_WGRAD_HL, DCN_HL_PRODUCERS, DCN_HL_ONLY_MID, DCN_STEM_POOL_FUSED, DCN_BN_REVERSE, DCN_BN_NT, DCN_BN_REDUCE_WIDE, DCN_WSPLIT_OVERLAP,
+ * DCN_BN_BWD_LEAN (0: the batch-norm backward kernels never run their <= 48-VGPR instances beside the side stream's weight-gradient
+ * GEMMs), DCN_BN_BWD_LEAN_MASK (which of them do: 1 reduce, 2 finalize, 4 blocked apply) -- are read ONCE, at the first call that needs them -- never on the
  * launch path.  dcn_reload_env re-reads them (tests / tuning scripts that change a variable in-process); not to be called
  * while another thread is inside the library. */
 void dcn_reload_env(void);
@@ -535,6 +537,18 @@ int dcn_bn_backward(const float* dy, const unsigned char* relu_mask, const float
 int dcn_bn_backward_from_partial(const float* dy, const float* bn_partial, int mtiles, const float* x, const float* stats,
                                  const float* gamma, int c, int64_t rows, float* dgamma, float* dbeta, float* dx,
                                  void* workspace, void* stream);
+/* dcn_bn_backward with every optional input and output of the engine's batch-norm backward step (tests of its kernel variants):
+ * the upstream gradient is dy (+ dy2), masked by relu_mask (bytes of dcn_bn_forward) or else by relu_out > 0 or not at all;
+ * groups (1 | 2) batches stacked along the rows, stats [groups][4][c]; absmax (optional): one float, raised to a bound of
+ * max |dx|; dq (optional, with absmax): dx as the pixel-blocked split-fp16 image, 4 * c * round_up(rows, 4) bytes; hl_dx
+ * (optional, with absmax, c % 32 == 0): dx as the hl32 image, 4 * c * rows bytes -- dx itself may then be null unless keep_dx.
+ * With two groups and dq / hl_dx, rows / groups must be a multiple of 4.  workspace: dcn_bn_backward_full_workspace bytes;
+ * its last groups * 3 * c floats receive the coefficients k1, k2, k3 of the apply pass, [groups][3][c]. */
+size_t dcn_bn_backward_full_workspace(int64_t rows, int c, int groups);
+int dcn_bn_backward_full(const float* dy, const float* dy2, const float* relu_out, const unsigned char* relu_mask,
+                         const float* x, const float* stats, const float* gamma, int c, int64_t rows, int groups,
+                         float* dgamma, float* dbeta, float* dx, float* g_out, float* absmax, void* dq, void* hl_dx,
+                         int keep_dx, void* workspace, void* stream);
 /* 3x3 / stride 2 / pad 1 max pool (kernel K2) of in [n,hin,win,c] -> out [n,(hin+1)/2,(win+1)/2,c]; argmax (nullable in
  * forward): one byte per output element (window position 0..8); backward gathers with it (deterministic). */
 int dcn_maxpool_forward(const float* in, int n, int hin, int win, int c, float* out, unsigned char* argmax, void* stream);

@@ -1214,7 +1214,8 @@ int backward_impl(dcn_plan* plan, const float* grad_descriptors, const float* gr
         dcn::launch_bn_bwd(dy, relu_out, mask, R.S(c.x), s, R.P(b.g), b.C, b.rows, p.groups, part, grads[b.g],
                            grads[b.b], k123, dx, g_out, f16 ? amax + c.idx : nullptr,
                            (f16 && !hl_w) ? (void*)dqbuf[cur] : nullptr, st, tiles, dy2,
-                           (hl_d || hl_w) ? (void*)hlimg[cur] : nullptr, hl_d ? 0 : 1);
+                           (hl_d || hl_w) ? (void*)hlimg[cur] : nullptr, hl_d ? 0 : 1,
+                           (overlap && dcn::tuning().bn_bwd_lean != 0) ? dcn::tuning().bn_bwd_lean_mask : 0);   // (lean instances beside the side stream's GEMMs)
         if (overlap) RT(hipEventRecord(p.ev_dq[cur], st));
         ++n_bn;
         dq_of = (f16 && !hl_w) ? dx : nullptr;   // the pixel-blocked split copy of this dx now sits in dqbuf[cur]

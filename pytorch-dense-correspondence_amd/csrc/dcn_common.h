@@ -14,6 +14,17 @@
 #define DCN_OPAQUE_INT(v) asm volatile("" : "+v"(v))   // the optimiser forgets what it knew about v (no loop-invariant hoisting)
 #endif
 
+// Register cap of a kernel (the allocator's budget, in VGPRs per lane).  Empty in the host emulation, which compiles the
+// same sources for the CPU.
+#if defined(DCN_HOSTEMU_BUILD)
+#define DCN_MAX_VGPRS(n)
+#else
+#define DCN_MAX_VGPRS(n) __attribute__((amdgpu_num_vgpr(n)))
+#endif
+
+// Nothing is scheduled across this point: neither by the instruction scheduler nor (memory accesses) by the passes in front of it.
+#define DCN_SCHED_FENCE() do { asm volatile("" ::: "memory"); __builtin_amdgcn_sched_barrier(0); } while (0)
+
 namespace dcn {
 
 constexpr int kWave = 64;  // CDNA wavefront

@@ -66,6 +66,13 @@
 //                           the forward apply pass, 2: dy and the conv output in the backward apply pass)
 //   DCN_WSPLIT_OVERLAP      0: the per-call weight images are made on the caller's stream in front of the forward / backward pass
 //                           (default 1: all of them on the side stream during the stem of the forward pass)
+//   DCN_BN_BWD_LEAN         0: the batch-norm backward passes always run their full-width instances.  1 (default): while the
+//                           backward pass runs its weight-gradient GEMMs on the side stream (DCN_BACKWARD_OVERLAP), the kernels named
+//                           by DCN_BN_BWD_LEAN_MASK run the instances that allocate <= 48 VGPRs -- what a SIMD has left beside a
+//                           resident weight-gradient workgroup (2 x 232 of 512) -- and so are placed on a CU while that GEMM runs
+//                           instead of queueing behind its round.  The stand-alone dcn_bn_backward* calls follow the two switches
+//                           alone.  Same results bit for bit.
+//   DCN_BN_BWD_LEAN_MASK    which kernels DCN_BN_BWD_LEAN covers: 1 the reduction, 2 finalize, 4 the blocked apply pass (default 7)
 #pragma once
 
 namespace dcn {
@@ -108,6 +115,8 @@ struct Tuning {
     int wsplit_overlap = 1;      // see DCN_WSPLIT_OVERLAP above
     int bn_nt = 0;               // see DCN_BN_NT above
     int bn_reverse = 0;          // see DCN_BN_REVERSE above
+    int bn_bwd_lean = 1;         // see DCN_BN_BWD_LEAN above
+    int bn_bwd_lean_mask = 7;    // see DCN_BN_BWD_LEAN_MASK above
     int wgrad_roles = 1;         // wide tile: wavefronts 0-3 stage the activations, 4-7 the gradient (0: copy spread over all 8)
 };
 

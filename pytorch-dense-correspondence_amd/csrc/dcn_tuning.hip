@@ -70,6 +70,8 @@ void read_env(Tuning& t) {
     if (const char* e = getenv("DCN_BN_NT")) t.bn_nt = atoi(e);
     if (const char* e = getenv("DCN_WSPLIT_OVERLAP")) t.wsplit_overlap = atoi(e) != 0;
     if (const char* e = getenv("DCN_BN_REDUCE_WIDE")) t.bn_reduce_wide = atoi(e);
+    if (const char* e = getenv("DCN_BN_BWD_LEAN")) t.bn_bwd_lean = atoi(e) != 0;
+    if (const char* e = getenv("DCN_BN_BWD_LEAN_MASK")) t.bn_bwd_lean_mask = atoi(e) & 7;
 }
 
 }  // namespace

@@ -56,7 +56,9 @@ void launch_bn_bwd(const float* dy, const float* relu_out, const unsigned char* 
                    int reduced_tiles_per_group = 0,                          // pixel-blocked split-fp16 tensor (f16_split.h)
                    const float* dy2 = nullptr,    // dy2 (optional): the upstream gradient is dy + dy2 (residual branch's share)
                    void* hl_dx = nullptr,         // hl_dx (optional, with dq; C % 32 == 0): dx also as the hl32 image the pre-split
-                   int keep_dx = 0);              // dgrad reads; the fp32 dx is then NOT written unless keep_dx
+                   int keep_dx = 0,               // dgrad reads; the fp32 dx is then NOT written unless keep_dx
+                   int lean = 0);                 // lean: bit mask of the kernels that run their <= 48-VGPR instance -- 1 reduce,
+                                                  // 2 finalize, 4 blocked apply -- with the same bits (DCN_BN_BWD_LEAN)
 // reduced_tiles_per_group > 0: `partial` already holds that many rows per group of per-tile sums, written by the epilogue
 // of the dgrad that produced dy (GemmConv::bnb_partial) -- the reduce pass is skipped; dy is then already ReLU-masked
 // (pass relu_out = relu_mask = nullptr)

@@ -297,19 +297,24 @@ __device__ __forceinline__ float4 load_dy(const float* __restrict__ dy, const fl
 // work-item (c4 = tid % CQ, rl = tid / CQ): CQ channel quads x 256 / CQ row lanes; grid = (C / (4 CQ) groups, chunks).
 // CQ = 16 (64 channels per workgroup) is the general shape; the wider ones (round 4) make a workgroup read WHOLE rows of up
 // to 512 channels -- one contiguous stream per tensor instead of 256-byte pieces strided by the row pitch.
-template <int CQ>
-__global__ void __launch_bounds__(256)
-bn_bwd_reduce_kernel(const float* __restrict__ dy, const float* dy2, const float* __restrict__ relu_out,
-                     const unsigned char* __restrict__ relu_mask, const float* __restrict__ x,
-                     const float* __restrict__ mean, const float* __restrict__ invstd, int C, int64_t rows_per_group,
-                     int chunks_per_group, int gstride, int rows_per_chunk, float* __restrict__ partial) {
-    constexpr int RL = 256 / CQ;
+//
+// LEAN (all three backward kernels, DCN_BN_BWD_LEAN): the same work-items, the same arithmetic and the same order of every
+// addition, scheduled for at most 48 VGPRs -- what a SIMD has left beside the two wavefronts (2 x 232 of 512 registers) that a
+// resident weight-gradient workgroup of the side stream puts on it (wgrad_hl_kernels.hip), so that these streaming passes are
+// placed on a CU while that GEMM runs instead of queueing behind its round.  Bit-identical results by construction.
+template <int CQ, bool LEAN>
+__device__ __forceinline__ void
+bn_bwd_reduce_body(const float* __restrict__ dy, const float* dy2, const float* __restrict__ relu_out,
+                   const unsigned char* __restrict__ relu_mask, const float* __restrict__ x,
+                   const float* __restrict__ mean, const float* __restrict__ invstd, int C, int64_t rows_per_group,
+                   int chunks_per_group, int gstride, int rows_per_chunk, float* __restrict__ partial) {
+    constexpr int RL = 256 / CQ, UF = LEAN ? 1 : RL;   // (UF: unroll factor of the LDS fold)
     __shared__ float4 s_g[RL][CQ];
     __shared__ float4 s_gx[RL][CQ];
     __shared__ float4 s_mg[RL][CQ];
     __shared__ float4 s_mx[RL][CQ];
-    const int c4 = threadIdx.x % CQ, rl = threadIdx.x / CQ;
-    const int c = blockIdx.x * (4 * CQ) + c4 * 4;
+    int c4 = threadIdx.x % CQ, rl = threadIdx.x / CQ;
+    int c = blockIdx.x * (4 * CQ) + c4 * 4;
     float4 ag = make_float4(0.f, 0.f, 0.f, 0.f), agx = ag, mg = ag, mx = ag;
     if (c < C) {
         const int g = (int)blockIdx.y / chunks_per_group;            // chunks never straddle a group boundary
@@ -318,20 +323,67 @@ bn_bwd_reduce_kernel(const float* __restrict__ dy, const float* dy2, const float
         const int64_t r0 = g * rows_per_group + (int64_t)((int)blockIdx.y - g * chunks_per_group) * rows_per_chunk;
         int64_t r1 = r0 + rows_per_chunk;
         if (r1 > (g + 1) * rows_per_group) r1 = (g + 1) * rows_per_group;
+        // the rows of this work-item, in order.  LEAN: one row at a time with its loads issued together -- the loop is instantiated
+        // per combination of the optional inputs (they are uniform), so that no branch sits between a row's loads
+        auto walk = [&](const float* dy2_, const float* relu_out_, const unsigned char* relu_mask_) {
 #pragma unroll 4   // (8 loads in flight per work-item instead of 2: 27 -> 23 us per launch)
-        for (int64_t r = r0 + rl; r < r1; r += RL) {
-            const int64_t o = r * C + c;
-            const float4 g = relu_masked(load_dy(dy, dy2, o >> 2), relu_out, relu_mask, o >> 2);
-            const float4 v = *reinterpret_cast<const float4*>(x + o);
-            const float4 xh = make_float4((v.x - mu.x) * is.x, (v.y - mu.y) * is.y, (v.z - mu.z) * is.z, (v.w - mu.w) * is.w);
-            ag.x += g.x; ag.y += g.y; ag.z += g.z; ag.w += g.w;
-            agx.x = fmaf(g.x, xh.x, agx.x); agx.y = fmaf(g.y, xh.y, agx.y);
-            agx.z = fmaf(g.z, xh.z, agx.z); agx.w = fmaf(g.w, xh.w, agx.w);
-            mg.x = fmaxf(mg.x, fabsf(g.x)); mg.y = fmaxf(mg.y, fabsf(g.y));
-            mg.z = fmaxf(mg.z, fabsf(g.z)); mg.w = fmaxf(mg.w, fabsf(g.w));
-            mx.x = fmaxf(mx.x, fabsf(xh.x)); mx.y = fmaxf(mx.y, fabsf(xh.y));
-            mx.z = fmaxf(mx.z, fabsf(xh.z)); mx.w = fmaxf(mx.w, fabsf(xh.w));
-        }
+            for (int64_t r = r0 + rl; r < r1; r += RL) {
+                const int64_t o = r * C + c;
+                const float4 g = relu_masked(load_dy(dy, dy2_, o >> 2), relu_out_, relu_mask_, o >> 2);
+                const float4 v = *reinterpret_cast<const float4*>(x + o);
+                const float4 xh = make_float4((v.x - mu.x) * is.x, (v.y - mu.y) * is.y, (v.z - mu.z) * is.z, (v.w - mu.w) * is.w);
+                ag.x += g.x; ag.y += g.y; ag.z += g.z; ag.w += g.w;
+                agx.x = fmaf(g.x, xh.x, agx.x); agx.y = fmaf(g.y, xh.y, agx.y);
+                agx.z = fmaf(g.z, xh.z, agx.z); agx.w = fmaf(g.w, xh.w, agx.w);
+                mg.x = fmaxf(mg.x, fabsf(g.x)); mg.y = fmaxf(mg.y, fabsf(g.y));
+                mg.z = fmaxf(mg.z, fabsf(g.z)); mg.w = fmaxf(mg.w, fabsf(g.w));
+                mx.x = fmaxf(mx.x, fabsf(xh.x)); mx.y = fmaxf(mx.y, fabsf(xh.y));
+                mx.z = fmaxf(mx.z, fabsf(xh.z)); mx.w = fmaxf(mx.w, fabsf(xh.w));
+            }
+        };
+        // LEAN: the same rows through chunk-relative 32-bit offsets (the chunk's first row is uniform: one base per tensor in
+        // scalar registers and ONE offset register per work-item instead of a 64-bit address per tensor)
+        auto walk_lean = [&](const float* dy2_, const float* relu_out_, const unsigned char* relu_mask_) {
+            const int64_t e0 = r0 * C;   // (a multiple of 4)
+            const float* dy_c = dy + e0;
+            const float* x_c = x + e0;
+            if (dy2_) dy2_ += e0;
+            if (relu_out_) relu_out_ += e0;
+            if (relu_mask_) relu_mask_ += e0 >> 2;
+            const unsigned n = r1 > r0 ? (unsigned)(r1 - r0) : 0u;   // (a capped chunk count can leave the last chunks of a group empty)
+            auto at = [](const float* p, unsigned bytes) { return p ? reinterpret_cast<const float*>(reinterpret_cast<const char*>(p) + bytes) : p; };
+#pragma unroll 1
+            for (unsigned r = rl; r < n; r += RL) {
+                const unsigned o = r * (unsigned)C + (unsigned)c;   // (a chunk is far below 4 GB)
+                float4 v = *reinterpret_cast<const float4*>(at(x_c, 4u * o));
+                const float4 g0 = load_dy(at(dy_c, 4u * o), at(dy2_, 4u * o), 0);
+                if (relu_out_) DCN_SCHED_FENCE();   // (a fourth 16-byte load per row only once dy2's registers are free again)
+                float4 g = relu_masked(g0, at(relu_out_, 4u * o), relu_mask_ ? relu_mask_ + (o >> 2) : relu_mask_, 0);
+                // (the maxima are touched only once the row has arrived: their in-flight copies would cost eight registers)
+                DCN_OPAQUE_INT(g.x); DCN_OPAQUE_INT(g.y); DCN_OPAQUE_INT(g.z); DCN_OPAQUE_INT(g.w);
+                DCN_OPAQUE_INT(v.x); DCN_OPAQUE_INT(v.y); DCN_OPAQUE_INT(v.z); DCN_OPAQUE_INT(v.w);
+                DCN_OPAQUE_INT(mg.x); DCN_OPAQUE_INT(mg.y); DCN_OPAQUE_INT(mg.z); DCN_OPAQUE_INT(mg.w);
+                DCN_OPAQUE_INT(mx.x); DCN_OPAQUE_INT(mx.y); DCN_OPAQUE_INT(mx.z); DCN_OPAQUE_INT(mx.w);
+                const float4 xh = make_float4((v.x - mu.x) * is.x, (v.y - mu.y) * is.y, (v.z - mu.z) * is.z, (v.w - mu.w) * is.w);
+                ag.x += g.x; ag.y += g.y; ag.z += g.z; ag.w += g.w;
+                agx.x = fmaf(g.x, xh.x, agx.x); agx.y = fmaf(g.y, xh.y, agx.y);
+                agx.z = fmaf(g.z, xh.z, agx.z); agx.w = fmaf(g.w, xh.w, agx.w);
+                mg.x = fmaxf(mg.x, fabsf(g.x)); mg.y = fmaxf(mg.y, fabsf(g.y));
+                mg.z = fmaxf(mg.z, fabsf(g.z)); mg.w = fmaxf(mg.w, fabsf(g.w));
+                mx.x = fmaxf(mx.x, fabsf(xh.x)); mx.y = fmaxf(mx.y, fabsf(xh.y));
+                mx.z = fmaxf(mx.z, fabsf(xh.z)); mx.w = fmaxf(mx.w, fabsf(xh.w));
+            }
+        };
+        if (!LEAN) walk(dy2, relu_out, relu_mask);
+        else if (relu_mask) { if (dy2) walk_lean(dy2, nullptr, relu_mask); else walk_lean(nullptr, nullptr, relu_mask); }
+        else if (relu_out) { if (dy2) walk_lean(dy2, relu_out, nullptr); else walk_lean(nullptr, relu_out, nullptr); }
+        else { if (dy2) walk_lean(dy2, nullptr, nullptr); else walk_lean(nullptr, nullptr, nullptr); }
+    }
+    if (LEAN) {   // (the work-item's indices again from its id: nothing but the sums lives across the row loop)
+        int t = threadIdx.x;
+        DCN_OPAQUE_INT(t);
+        c4 = t % CQ; rl = t / CQ;
+        c = blockIdx.x * (4 * CQ) + c4 * 4;
     }
     s_g[rl][c4] = ag;
     s_gx[rl][c4] = agx;
@@ -339,6 +391,7 @@ bn_bwd_reduce_kernel(const float* __restrict__ dy, const float* dy2, const float
     s_mx[rl][c4] = mx;
     __syncthreads();
     if (rl == 0 && c < C) {
+#pragma unroll UF   // (LEAN: one row lane's four float4 at a time, in the same order)
         for (int i = 1; i < RL; ++i) {
             const float4 a = s_g[i][c4], b = s_gx[i][c4], m1 = s_mg[i][c4], m2 = s_mx[i][c4];
             ag.x += a.x; ag.y += a.y; ag.z += a.z; ag.w += a.w;
@@ -353,16 +406,30 @@ bn_bwd_reduce_kernel(const float* __restrict__ dy, const float* dy2, const float
         p[3] = make_float4(ag.w, agx.w, mg.w, mx.w);
     }
 }
+#define DCN_BN_RED_ARGS const float* __restrict__ dy, const float* dy2, const float* __restrict__ relu_out,                    \
+                        const unsigned char* __restrict__ relu_mask, const float* __restrict__ x,                              \
+                        const float* __restrict__ mean, const float* __restrict__ invstd, int C, int64_t rows_per_group,       \
+                        int chunks_per_group, int gstride, int rows_per_chunk, float* __restrict__ partial
+#define DCN_BN_RED_PASS dy, dy2, relu_out, relu_mask, x, mean, invstd, C, rows_per_group, chunks_per_group, gstride, rows_per_chunk, partial
+template <int CQ>
+__global__ void __launch_bounds__(256)
+bn_bwd_reduce_kernel(DCN_BN_RED_ARGS) { bn_bwd_reduce_body<CQ, false>(DCN_BN_RED_PASS); }
+template <int CQ>
+__global__ void __launch_bounds__(256) DCN_MAX_VGPRS(48)
+bn_bwd_reduce_lean_kernel(DCN_BN_RED_ARGS) { bn_bwd_reduce_body<CQ, true>(DCN_BN_RED_PASS); }
+#undef DCN_BN_RED_ARGS
+#undef DCN_BN_RED_PASS
 
 // partial[chunk][C][4] -> dgamma, dbeta and the coefficients of the apply pass:
 //   dx = k1 * (g - k2 - xhat * k3),  k1 = gamma*invstd, k2 = sum_g / M, k3 = sum_gx / M
 // and, when absmax is given, raises absmax[0] to  max_c |k1| (max|g| + |k2| + max|xhat| |k3|)  >=  max |dx|  (the
 // pre-scale of the split-fp16 convolutions only needs an upper bound within a small factor of the true abs-max).
-__global__ void __launch_bounds__(256)
-bn_bwd_finalize_kernel(const float* __restrict__ partial, int chunks, int groups, int C, double count,
-                       const float* __restrict__ gamma, const float* __restrict__ invstd, int gstride,
-                       float* __restrict__ dgamma, float* __restrict__ dbeta, float* __restrict__ k123,
-                       float* __restrict__ absmax) {
+template <bool LEAN>
+__device__ __forceinline__ void
+bn_bwd_finalize_body(const float* __restrict__ partial, int chunks, int groups, int C, double count,
+                     const float* __restrict__ gamma, const float* __restrict__ invstd, int gstride,
+                     float* __restrict__ dgamma, float* __restrict__ dbeta, float* __restrict__ k123,
+                     float* __restrict__ absmax) {
     // 4 channels x 64 chunk-parts per workgroup (see bn_finalize_kernel).  Per group g (chunks [g*chunks, (g+1)*chunks)):
     // k123[g][0..2][C]; dgamma / dbeta are the sums over the groups (the parameters are shared).
     __shared__ double s_a[4][4];
@@ -370,12 +437,13 @@ bn_bwd_finalize_kernel(const float* __restrict__ partial, int chunks, int groups
     __shared__ float s_mg[4][4];
     __shared__ float s_mx[4][4];
     const int cl = threadIdx.x & 3, part = threadIdx.x >> 2, wv = threadIdx.x >> 6;
-    const int c = blockIdx.x * 4 + cl;
+    int c = blockIdx.x * 4 + cl;
     const bool lead = threadIdx.x < 4 && c < C;
     // (round 6: requested in the shadow of the partial loads, see bn_finalize_kernel; at most two groups)
-    const float pre_gamma = lead ? gamma[c] : 0.f;
-    const float pre_is0 = lead ? invstd[c] : 0.f, pre_is1 = (lead && groups > 1) ? invstd[gstride + c] : 0.f;
-    const unsigned pre_bound = (threadIdx.x == 0 && absmax) ? __atomic_load_n(reinterpret_cast<unsigned*>(absmax), __ATOMIC_RELAXED) : 0u;
+    // (LEAN: nothing is requested ahead -- the same words are read where they are used)
+    const float pre_gamma = (!LEAN && lead) ? gamma[c] : 0.f;
+    const float pre_is0 = (!LEAN && lead) ? invstd[c] : 0.f, pre_is1 = (!LEAN && lead && groups > 1) ? invstd[gstride + c] : 0.f;
+    const unsigned pre_bound = (!LEAN && threadIdx.x == 0 && absmax) ? __atomic_load_n(reinterpret_cast<unsigned*>(absmax), __ATOMIC_RELAXED) : 0u;
     double tot_a = 0.0, tot_b = 0.0;
     float bound = 0.f;
     for (int g = 0; g < groups; ++g) {
@@ -386,15 +454,24 @@ bn_bwd_finalize_kernel(const float* __restrict__ partial, int chunks, int groups
             // compiler had turned the `#pragma unroll 4` loop into load | wait | add | load | wait ... -- five dependent memory
             // round trips for the five chunks a work-item owns at eight images: that WAS the kernel's 8 us
             const int t_end = (g + 1) * chunks;
-            for (int t0 = g * chunks + part; t0 < t_end; t0 += 64 * 8) {
-                float4 buf[8];
+            // (LEAN: the same eight rows as two batches of four -- same rows, same order of the additions, half the registers)
+            constexpr int NB = LEAN ? 4 : 8;
+            for (int t0 = g * chunks + part; t0 < t_end; t0 += 64 * NB) {
+                float4 buf[NB];
 #pragma unroll
-                for (int u = 0; u < 8; ++u) {
+                for (int u = 0; u < NB; ++u) {
                     const int t = min(t0 + 64 * u, t_end - 1);   // (straight-line loads: a row past the end re-reads the last one ...)
-                    buf[u] = reinterpret_cast<const float4*>(partial)[(int64_t)t * C + c];
+                    if (LEAN)   // (a 32-bit byte offset from the one base: the partial sums of a layer are a few MB)
+                        buf[u] = *reinterpret_cast<const float4*>(reinterpret_cast<const char*>(partial) + 16u * (unsigned)(t * C + c));
+                    else
+                        buf[u] = reinterpret_cast<const float4*>(partial)[(int64_t)t * C + c];
+                }
+                if (LEAN) {   // (all four requested before the first is used: none of them moves into its `if` below)
+#pragma unroll
+                    for (int u = 0; u < NB; ++u) { DCN_OPAQUE_INT(buf[u].x); DCN_OPAQUE_INT(buf[u].y); DCN_OPAQUE_INT(buf[u].z); DCN_OPAQUE_INT(buf[u].w); }
                 }
 #pragma unroll
-                for (int u = 0; u < 8; ++u) {
+                for (int u = 0; u < NB; ++u) {
                     if (t0 + 64 * u < t_end) {                  // (... and is not added)
                         a += (double)buf[u].x;
                         b += (double)buf[u].y;
@@ -402,6 +479,7 @@ bn_bwd_finalize_kernel(const float* __restrict__ partial, int chunks, int groups
                         mx = fmaxf(mx, buf[u].w);
                     }
                 }
+                if (LEAN) __builtin_amdgcn_sched_barrier(0);   // (the next batch's loads stay behind this batch's additions)
             }
         }
         a = part_tree_sum(a);
@@ -412,13 +490,24 @@ bn_bwd_finalize_kernel(const float* __restrict__ partial, int chunks, int groups
         if ((threadIdx.x & 63) < 4) { s_a[wv][cl] = a; s_b[wv][cl] = b; s_mg[wv][cl] = mg; s_mx[wv][cl] = mx; }
         __syncthreads();
         if (lead) {
+            if (LEAN) DCN_OPAQUE_INT(c);   // (no address of this block is formed ahead of the partial loads and kept in registers)
             a = (s_a[0][cl] + s_a[1][cl]) + (s_a[2][cl] + s_a[3][cl]);
+            if (LEAN) DCN_SCHED_FENCE();   // (one of the four folds at a time)
             b = (s_b[0][cl] + s_b[1][cl]) + (s_b[2][cl] + s_b[3][cl]);
+            if (LEAN) DCN_SCHED_FENCE();
             mg = fmaxf(fmaxf(s_mg[0][cl], s_mg[1][cl]), fmaxf(s_mg[2][cl], s_mg[3][cl]));
+            if (LEAN) DCN_SCHED_FENCE();
             mx = fmaxf(fmaxf(s_mx[0][cl], s_mx[1][cl]), fmaxf(s_mx[2][cl], s_mx[3][cl]));
-            float is_g = g == 0 ? pre_is0 : (g == 1 ? pre_is1 : invstd[g * gstride + c]), gam = pre_gamma;
+            if (LEAN) DCN_SCHED_FENCE();
+            float is_g = LEAN ? invstd[g * gstride + c] : (g == 0 ? pre_is0 : (g == 1 ? pre_is1 : invstd[g * gstride + c]));
+            float gam = LEAN ? gamma[c] : pre_gamma;
             DCN_OPAQUE_INT(is_g); DCN_OPAQUE_INT(gam);
-            const float c1 = gam * is_g, c2 = (float)(a / count), c3 = (float)(b / count);
+            if (LEAN) __builtin_amdgcn_sched_barrier(0);   // (the two fp64 divisions one after the other: each takes a dozen registers)
+            const float c1 = gam * is_g;
+            float c2 = (float)(a / count);
+            if (LEAN) { DCN_OPAQUE_INT(c2); __builtin_amdgcn_sched_barrier(0); }
+            float c3 = (float)(b / count);
+            if (LEAN) { DCN_OPAQUE_INT(c3); __builtin_amdgcn_sched_barrier(0); }
             float* k = k123 + (int64_t)g * 3 * C;
             k[c] = c1;
             k[C + c] = c2;
@@ -429,6 +518,7 @@ bn_bwd_finalize_kernel(const float* __restrict__ partial, int chunks, int groups
         }
     }
     if (lead) {
+        if (LEAN) DCN_OPAQUE_INT(c);
         dbeta[c] = (float)tot_a;
         dgamma[c] = (float)tot_b;
     }
@@ -437,11 +527,22 @@ bn_bwd_finalize_kernel(const float* __restrict__ partial, int chunks, int groups
         bound = fmaxf(bound, __shfl_xor(bound, 2));
         if (threadIdx.x == 0) {
             const unsigned bits = __float_as_uint(bound);
-            if (bound > 0.f && bits > pre_bound)   // (a stale word only costs a redundant atomicMax)
+            const unsigned seen = LEAN ? __atomic_load_n(reinterpret_cast<unsigned*>(absmax), __ATOMIC_RELAXED) : pre_bound;
+            if (bound > 0.f && bits > seen)   // (a stale word only costs a redundant atomicMax)
                 atomicMax(reinterpret_cast<unsigned*>(absmax), bits);
         }
     }
 }
+#define DCN_BN_FIN_ARGS const float* __restrict__ partial, int chunks, int groups, int C, double count,                        \
+                        const float* __restrict__ gamma, const float* __restrict__ invstd, int gstride,                        \
+                        float* __restrict__ dgamma, float* __restrict__ dbeta, float* __restrict__ k123, float* __restrict__ absmax
+#define DCN_BN_FIN_PASS partial, chunks, groups, C, count, gamma, invstd, gstride, dgamma, dbeta, k123, absmax
+__global__ void __launch_bounds__(256)
+bn_bwd_finalize_kernel(DCN_BN_FIN_ARGS) { bn_bwd_finalize_body<false>(DCN_BN_FIN_PASS); }
+__global__ void __launch_bounds__(256) DCN_MAX_VGPRS(48)
+bn_bwd_finalize_lean_kernel(DCN_BN_FIN_ARGS) { bn_bwd_finalize_body<true>(DCN_BN_FIN_PASS); }
+#undef DCN_BN_FIN_ARGS
+#undef DCN_BN_FIN_PASS
 
 // dx = k1*(g - k2 - (x-mean)*invstd*k3); optionally also writes g (the relu-masked upstream gradient) for the
 // residual branch.
@@ -476,14 +577,16 @@ bn_bwd_apply_kernel(const float* __restrict__ dy, const float* dy2, const float*
 // The same pass for the split-fp16 convolution mode: one work-item per (pixel quad, channel quad) so that it can ALSO emit
 // dx as the pixel-blocked split tensor wgrad consumes (f16_split.h), scaled by the power of two chosen from the bound the
 // finalize kernel has just stored in *absmax -- no separate split pass over dx.  rows_per_group % 4 == 0 when grouped.
-__global__ void __launch_bounds__(256)
-bn_bwd_apply_blocked_kernel(const float* __restrict__ dy, const float* dy2, const float* __restrict__ relu_out,
-                            const unsigned char* __restrict__ relu_mask, const float* __restrict__ x,
-                            const float* __restrict__ mean, const float* __restrict__ invstd, const float* __restrict__ k1,
-                            const float* __restrict__ k2, const float* __restrict__ k3, float* __restrict__ dx,
-                            float* g_out, dcnsplit::u32x4* __restrict__ dq, const float* __restrict__ absmax,
-                            int c4n, int64_t rows, int64_t rows_per_group, int gstride, int kstride,
-                            dcnsplit::u32x2* __restrict__ hl, int rev, int nt) {
+// LEAN: one row in flight at a time, and the five per-channel constants re-loaded (cache hits) where each row uses them.
+template <bool LEAN, bool DQ>
+__device__ __forceinline__ void
+bn_bwd_apply_blocked_body(const float* __restrict__ dy, const float* dy2, const float* __restrict__ relu_out,
+                          const unsigned char* __restrict__ relu_mask, const float* __restrict__ x,
+                          const float* __restrict__ mean, const float* __restrict__ invstd, const float* __restrict__ k1,
+                          const float* __restrict__ k2, const float* __restrict__ k3, float* __restrict__ dx,
+                          float* g_out, dcnsplit::u32x4* __restrict__ dq, const float* __restrict__ absmax,
+                          int c4n, int64_t rows, int64_t rows_per_group, int gstride, int kstride,
+                          dcnsplit::u32x2* __restrict__ hl, int rev, int nt) {
     // hl (optional, c4n % 8 == 0): dx as the hl32 image the pre-split dgrad reads (same scale as dq); dx itself may then be
     // null -- nobody else reads the fp32 tensor
     const float s = dcnsplit::pow2_scale(*absmax);
@@ -493,29 +596,63 @@ bn_bwd_apply_blocked_kernel(const float* __restrict__ dy, const float* dy2, cons
         const int64_t q = i / c4n;
         const int cq = (int)(i - q * c4n);
         const bool second = q * 4 >= rows_per_group;
-        const int c = cq * 4 + (second ? gstride : 0), ck = cq * 4 + (second ? kstride : 0);
-        const float4 mu = *reinterpret_cast<const float4*>(mean + c);
-        const float4 is = *reinterpret_cast<const float4*>(invstd + c);
-        const float4 a = *reinterpret_cast<const float4*>(k1 + ck);
-        const float4 b = *reinterpret_cast<const float4*>(k2 + ck);
-        const float4 d = *reinterpret_cast<const float4*>(k3 + ck);
+        int c = cq * 4 + (second ? gstride : 0), ck = cq * 4 + (second ? kstride : 0);
+        float4 mu, is, a, b, d;
+        if (!LEAN) {
+            mu = *reinterpret_cast<const float4*>(mean + c);
+            is = *reinterpret_cast<const float4*>(invstd + c);
+            a = *reinterpret_cast<const float4*>(k1 + ck);
+            b = *reinterpret_cast<const float4*>(k2 + ck);
+            d = *reinterpret_cast<const float4*>(k3 + ck);
+        }
         float o[4][4];
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
             const int64_t m = q * 4 + r;
+            if (LEAN) __builtin_amdgcn_sched_barrier(0);   // (row r's loads stay behind row r - 1's stores)
             if (m < rows) {
                 const int64_t e = m * c4n + cq;
+
                 float4 g0 = ld4(dy, e, nt != 0);
                 if (dy2) {
                     const float4 h = reinterpret_cast<const float4*>(dy2)[e];
                     g0.x += h.x; g0.y += h.y; g0.z += h.z; g0.w += h.w;
                 }
-                const float4 g = relu_masked(g0, relu_out, relu_mask, e);
-                const float4 v = ld4(x, e, nt != 0);
-                o[r][0] = a.x * (g.x - b.x - (v.x - mu.x) * is.x * d.x);
-                o[r][1] = a.y * (g.y - b.y - (v.y - mu.y) * is.y * d.y);
-                o[r][2] = a.z * (g.z - b.z - (v.z - mu.z) * is.z * d.z);
-                o[r][3] = a.w * (g.w - b.w - (v.w - mu.w) * is.w * d.w);
+                float4 g = relu_masked(g0, relu_out, relu_mask, e);
+                float4 v = ld4(x, e, nt != 0);
+                if (LEAN) {   // the row's streamed operands first, THEN its five per-channel constants (cache hits, re-loaded per row)
+                    DCN_OPAQUE_INT(g.x); DCN_OPAQUE_INT(g.y); DCN_OPAQUE_INT(g.z); DCN_OPAQUE_INT(g.w);
+                    DCN_OPAQUE_INT(v.x); DCN_OPAQUE_INT(v.y); DCN_OPAQUE_INT(v.z); DCN_OPAQUE_INT(v.w);
+                    DCN_OPAQUE_INT(c); DCN_OPAQUE_INT(ck);
+                }
+                if (LEAN && DQ) {
+                    // beside the 4 x 4 block there is room for ONE constant at a time: the operations of the expression below, in its
+                    // order --  a * ((g - b) - (((v - mu) * is) * d))  -- each behind the load of its constant
+#define DCN_BN_STEP(dst, expr, ptr)                                                                                           \
+                    { const float4 k = *reinterpret_cast<const float4*>(ptr);                                                  \
+                      dst = expr;                                                                                              \
+                      DCN_OPAQUE_INT(dst.x); DCN_OPAQUE_INT(dst.y); DCN_OPAQUE_INT(dst.z); DCN_OPAQUE_INT(dst.w); }
+                    float4 t, u;
+                    DCN_BN_STEP(t, make_float4(v.x - k.x, v.y - k.y, v.z - k.z, v.w - k.w), mean + c)
+                    DCN_BN_STEP(t, make_float4(t.x * k.x, t.y * k.y, t.z * k.z, t.w * k.w), invstd + c)
+                    DCN_BN_STEP(t, make_float4(t.x * k.x, t.y * k.y, t.z * k.z, t.w * k.w), k3 + ck)
+                    DCN_BN_STEP(u, make_float4(g.x - k.x, g.y - k.y, g.z - k.z, g.w - k.w), k2 + ck)
+                    DCN_BN_STEP(t, make_float4(k.x * (u.x - t.x), k.y * (u.y - t.y), k.z * (u.z - t.z), k.w * (u.w - t.w)), k1 + ck)
+#undef DCN_BN_STEP
+                    o[r][0] = t.x; o[r][1] = t.y; o[r][2] = t.z; o[r][3] = t.w;
+                } else {
+                    if (LEAN) {
+                        mu = *reinterpret_cast<const float4*>(mean + c);
+                        is = *reinterpret_cast<const float4*>(invstd + c);
+                        a = *reinterpret_cast<const float4*>(k1 + ck);
+                        b = *reinterpret_cast<const float4*>(k2 + ck);
+                        d = *reinterpret_cast<const float4*>(k3 + ck);
+                    }
+                    o[r][0] = a.x * (g.x - b.x - (v.x - mu.x) * is.x * d.x);
+                    o[r][1] = a.y * (g.y - b.y - (v.y - mu.y) * is.y * d.y);
+                    o[r][2] = a.z * (g.z - b.z - (v.z - mu.z) * is.z * d.z);
+                    o[r][3] = a.w * (g.w - b.w - (v.w - mu.w) * is.w * d.w);
+                }
                 if (dx) reinterpret_cast<float4*>(dx)[e] = make_float4(o[r][0], o[r][1], o[r][2], o[r][3]);
                 if (g_out) reinterpret_cast<float4*>(g_out)[e] = g;
                 if (hl) {
@@ -529,9 +666,25 @@ bn_bwd_apply_blocked_kernel(const float* __restrict__ dy, const float* dy2, cons
                 o[r][0] = o[r][1] = o[r][2] = o[r][3] = 0.f;
             }
         }
-        if (dq) dcnsplit::store_blocked_quad(dq, q, cq, c4n, o, s);   // (null: the weight gradient reads the hl32 image)
+        if (DQ && dq) dcnsplit::store_blocked_quad(dq, q, cq, c4n, o, s);   // (null: the weight gradient reads the hl32 image)
     }
 }
+#define DCN_BN_APB_ARGS const float* __restrict__ dy, const float* dy2, const float* __restrict__ relu_out,                    \
+                        const unsigned char* __restrict__ relu_mask, const float* __restrict__ x,                              \
+                        const float* __restrict__ mean, const float* __restrict__ invstd, const float* __restrict__ k1,        \
+                        const float* __restrict__ k2, const float* __restrict__ k3, float* __restrict__ dx,                    \
+                        float* g_out, dcnsplit::u32x4* __restrict__ dq, const float* __restrict__ absmax,                      \
+                        int c4n, int64_t rows, int64_t rows_per_group, int gstride, int kstride,                               \
+                        dcnsplit::u32x2* __restrict__ hl, int rev, int nt
+#define DCN_BN_APB_PASS dy, dy2, relu_out, relu_mask, x, mean, invstd, k1, k2, k3, dx, g_out, dq, absmax, c4n, rows, rows_per_group, \
+                        gstride, kstride, hl, rev, nt
+__global__ void __launch_bounds__(256)
+bn_bwd_apply_blocked_kernel(DCN_BN_APB_ARGS) { bn_bwd_apply_blocked_body<false, true>(DCN_BN_APB_PASS); }
+template <bool DQ>   // (DQ false: dq is null -- the 4 x 4 block of the pixel-blocked image is not kept)
+__global__ void __launch_bounds__(256) DCN_MAX_VGPRS(48)
+bn_bwd_apply_blocked_lean_kernel(DCN_BN_APB_ARGS) { bn_bwd_apply_blocked_body<true, DQ>(DCN_BN_APB_PASS); }
+#undef DCN_BN_APB_ARGS
+#undef DCN_BN_APB_PASS
 
 // absmax[0] = max(absmax[0], max |v[i]|)
 __global__ void __launch_bounds__(256)
@@ -835,7 +988,7 @@ void launch_bn_bwd(const float* dy, const float* relu_out, const unsigned char* 
                    const float* gamma, int C,
                    int64_t rows, int groups, float* partial, float* dgamma, float* dbeta, float* k123, float* dx,
                    float* g_out, float* absmax, void* dq, hipStream_t st, int reduced_tiles_per_group, const float* dy2,
-                   void* hl_dx, int keep_dx) {
+                   void* hl_dx, int keep_dx, int lean) {
     const int64_t rpg = rows / groups;
     const float* mean = stats + 2 * C;
     const float* invstd = stats + 3 * C;
@@ -848,26 +1001,33 @@ void launch_bn_bwd(const float* dy, const float* relu_out, const unsigned char* 
         ObservedLaunch obs(DCN_PROF_BN_BWD_REDUCE, (double)rows * C * in_bytes, st);
         const int cap = tuning().bn_reduce_wide;   // DCN_BN_REDUCE_WIDE: 16 / 32 / 64 / 128 channel quads per workgroup at most
         const int cq = ((C % 512) == 0 && cap >= 128) ? 128 : (((C % 256) == 0 && cap >= 64) ? 64 : (((C % 128) == 0 && cap >= 32) ? 32 : 16));
-#define DCN_BN_RED(CQ)                                                                                                        \
-        hipLaunchKernelGGL(bn_bwd_reduce_kernel<CQ>, dim3(ceil_div(C, 4 * CQ), chunks * groups), dim3(256), 0, st, dy, dy2, relu_out, \
+#define DCN_BN_RED(K, CQ)                                                                                                     \
+        hipLaunchKernelGGL(K<CQ>, dim3(ceil_div(C, 4 * CQ), chunks * groups), dim3(256), 0, st, dy, dy2, relu_out,            \
                            relu_mask, x, mean, invstd, C, rpg, chunks, 4 * C, rpc, partial)
-        if (cq == 128) DCN_BN_RED(128);
-        else if (cq == 64) DCN_BN_RED(64);
-        else if (cq == 32) DCN_BN_RED(32);
-        else DCN_BN_RED(16);
+#define DCN_BN_RED_CQ(K)                                                                                                      \
+        if (cq == 128) DCN_BN_RED(K, 128);                                                                                    \
+        else if (cq == 64) DCN_BN_RED(K, 64);                                                                                 \
+        else if (cq == 32) DCN_BN_RED(K, 32);                                                                                 \
+        else DCN_BN_RED(K, 16)
+        if (lean & 1) { DCN_BN_RED_CQ(bn_bwd_reduce_lean_kernel); }
+        else { DCN_BN_RED_CQ(bn_bwd_reduce_kernel); }
+#undef DCN_BN_RED_CQ
 #undef DCN_BN_RED
     }
     {
         ObservedLaunch obs(DCN_PROF_BN_FINALIZE, 16.0 * (double)chunks * groups * C, st);
-        hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3(ceil_div(C, 4)), dim3(256), 0, st, (const float*)partial, chunks,
-                           groups, C, (double)rpg, gamma, invstd, 4 * C, dgamma, dbeta, k123, absmax);
+        const auto kernel = (lean & 2) ? bn_bwd_finalize_lean_kernel : bn_bwd_finalize_kernel;
+        hipLaunchKernelGGL(kernel, dim3(ceil_div(C, 4)), dim3(256), 0, st,
+                           (const float*)partial, chunks, groups, C, (double)rpg, gamma, invstd, 4 * C, dgamma, dbeta, k123, absmax);
     }
     const int64_t total4 = rows * (C / 4);
     if ((dq || (hl_dx && (C % 32) == 0)) && absmax) {
         const bool hl = hl_dx && (C % 32) == 0;
         ObservedLaunch obs(DCN_PROF_BN_BWD_APPLY, (double)rows * C * (in_bytes + ((hl && !keep_dx) ? 0.0 : 4.0) + (g_out ? 4.0 : 0.0) +
                                                                       (dq ? 4.0 : 0.0) + (hl ? 4.0 : 0.0)), st);
-        hipLaunchKernelGGL(bn_bwd_apply_blocked_kernel, dim3(blocks_for(((rows + 3) / 4) * (C / 4), kGridCap)), dim3(256), 0, st,
+        const auto kernel = !(lean & 4) ? bn_bwd_apply_blocked_kernel
+                                        : (dq ? bn_bwd_apply_blocked_lean_kernel<true> : bn_bwd_apply_blocked_lean_kernel<false>);
+        hipLaunchKernelGGL(kernel, dim3(blocks_for(((rows + 3) / 4) * (C / 4), kGridCap)), dim3(256), 0, st,
                            dy, dy2, relu_out, relu_mask, x, mean, invstd, (const float*)k123, (const float*)(k123 + C),
                            (const float*)(k123 + 2 * C), (hl_dx && (C % 32) == 0 && !keep_dx) ? nullptr : dx, g_out,
                            (dcnsplit::u32x4*)dq, (const float*)absmax, C / 4, rows, rpg, 4 * C, 3 * C,
@@ -990,7 +1150,7 @@ extern "C" int dcn_bn_backward(const float* dy, const unsigned char* relu_mask, 
     float* partial = (float*)workspace;
     float* k123 = partial + (size_t)dcn::bn_bwd_chunks(rows) * 4 * c;
     dcn::launch_bn_bwd(dy, nullptr, relu_mask, x, stats, gamma, c, rows, 1, partial, dgamma, dbeta, k123, dx, g_out, nullptr,
-                       nullptr, (hipStream_t)stream);
+                       nullptr, (hipStream_t)stream, 0, nullptr, nullptr, 0, dcn::tuning().bn_bwd_lean ? dcn::tuning().bn_bwd_lean_mask : 0);
     return dcn::check_launch();
 }
 
@@ -1003,7 +1163,32 @@ extern "C" int dcn_bn_backward_from_partial(const float* dy, const float* bn_par
         (c % 4) != 0 || rows < 1)
         return DCN_E_INVALID;
     dcn::launch_bn_bwd(dy, nullptr, nullptr, x, stats, gamma, c, rows, 1, const_cast<float*>(bn_partial), dgamma, dbeta,
-                       (float*)workspace, dx, nullptr, nullptr, nullptr, (hipStream_t)stream, mtiles);
+                       (float*)workspace, dx, nullptr, nullptr, nullptr, (hipStream_t)stream, mtiles, nullptr, nullptr, 0,
+                       dcn::tuning().bn_bwd_lean ? dcn::tuning().bn_bwd_lean_mask : 0);
+    return dcn::check_launch();
+}
+
+// every input and output of launch_bn_bwd as one stand-alone call (unit tests of the backward kernels' variants)
+extern "C" size_t dcn_bn_backward_full_workspace(int64_t rows, int c, int groups) {
+    if (rows < 1 || c < 4 || groups < 1 || (rows % groups) != 0) return 0;
+    return ((size_t)groups * dcn::bn_bwd_chunks(rows / groups) * 4 * (size_t)c + (size_t)groups * 3 * (size_t)c) * sizeof(float);
+}
+
+extern "C" int dcn_bn_backward_full(const float* dy, const float* dy2, const float* relu_out, const unsigned char* relu_mask,
+                                    const float* x, const float* stats, const float* gamma, int c, int64_t rows, int groups,
+                                    float* dgamma, float* dbeta, float* dx, float* g_out, float* absmax, void* dq, void* hl_dx,
+                                    int keep_dx, void* workspace, void* stream) {
+    if (!dy || !x || !stats || !gamma || !dgamma || !dbeta || !workspace || c < 4 || (c % 4) != 0 || rows < 1) return DCN_E_INVALID;
+    if ((groups != 1 && groups != 2) || (rows % groups) != 0) return DCN_E_INVALID;
+    const bool blocked = (dq || (hl_dx && (c % 32) == 0)) && absmax;
+    if ((dq || hl_dx) && !absmax) return DCN_E_INVALID;
+    if (hl_dx && (c % 32) != 0) return DCN_E_INVALID;
+    if (blocked && groups == 2 && ((rows / groups) % 4) != 0) return DCN_E_INVALID;
+    if (!dx && !(hl_dx && !keep_dx)) return DCN_E_INVALID;
+    float* partial = (float*)workspace;
+    float* k123 = partial + (size_t)groups * dcn::bn_bwd_chunks(rows / groups) * 4 * c;
+    dcn::launch_bn_bwd(dy, relu_out, relu_mask, x, stats, gamma, c, rows, groups, partial, dgamma, dbeta, k123, dx, g_out, absmax,
+                       dq, (hipStream_t)stream, 0, dy2, hl_dx, keep_dx, dcn::tuning().bn_bwd_lean ? dcn::tuning().bn_bwd_lean_mask : 0);
     return dcn::check_launch();
 }
 

@@ -131,6 +131,8 @@ SYMBOLS = {
                                       c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "dcn_bn_backward_from_partial": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int64,
                                              c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "dcn_bn_backward_full_workspace": (c_size_t, [c_int64, c_int, c_int]),
+    "dcn_bn_backward_full": (c_int, [c_void_p] * 7 + [c_int, c_int64, c_int] + [c_void_p] * 7 + [c_int, c_void_p, c_void_p]),
     "dcn_triplet_loss_workspace_bytes": (c_size_t, [c_int64]),
     "dcn_triplet_loss_forward": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p, c_int64, c_int64,
                                          c_float, c_void_p, c_void_p, c_void_p, c_void_p]),

@@ -1,5 +1,7 @@
 """Two-stream timeline of the last training step in a rocprofv3 --kernel-trace run (overlap on): per-queue busy time, union busy,
-gaps on the main queue, kernel time by name and queue.  python tools/timeline_summary.py <rocprofv3 output dir>"""
+gaps on the main queue, kernel time by name and queue, and -- for every batch-norm backward launch on the main queue -- how long
+it waited behind its predecessor, how long it ran, and whether a weight-gradient kernel of the side queue was running meanwhile.
+python tools/timeline_summary.py <rocprofv3 output dir>"""
 import csv, glob, collections, sys
 f=glob.glob(sys.argv[1]+'/*/*_kernel_trace.csv')[0]
 rows=list(csv.DictReader(open(f)))
@@ -37,3 +39,26 @@ agg=collections.defaultdict(lambda:[0,0])
 for r in seg:
     k=(r['q'],r['Kernel_Name'].split('(')[0][:60]); agg[k][0]+=1; agg[k][1]+=r['e']-r['s']
 for k,v in sorted(agg.items(), key=lambda kv:-kv[1][1])[:30]: print('%-8s %-62s n=%3d %.3f ms'%(k[0],k[1],v[0],v[1]/1e6))
+# batch-norm backward launches on the main queue against the side queue's weight-gradient kernels
+def short(n): return n.split('(')[0].replace('void dcn::','')[:34]
+side=[r for r in seg if r['q']!=main[0]['q'] and 'wgrad' in r['Kernel_Name']]
+def under(s,e):   # (ns of [s, e) covered by a running side-queue weight-gradient kernel, name of the longest cover)
+    tot=0; best=(0,'-')
+    for w in side:
+        o=min(e,w['e'])-max(s,w['s'])
+        if o>0: tot+=o; best=max(best,(o,short(w['Kernel_Name'])))
+    return min(tot,max(e-s,0)),best[1]
+print('batch-norm backward launches (main queue): wait = predecessor end -> start, run = start -> end; "under" = share of it with a side-queue wgrad kernel running')
+print('%8s %-34s %8s %8s %8s %8s  %s'%('@ms','kernel','wait us','under','run us','under','side-queue kernel'))
+tot=collections.defaultdict(lambda:[0,0,0,0,0]); wsum=0
+for a,b in zip(main,main[1:]):
+    if 'bn_bwd_' not in b['Kernel_Name']: continue
+    ws,we=min(a['e'],b['s']),b['s']
+    wu,_=under(ws,we); ru,nm=under(b['s'],b['e'])
+    k=short(b['Kernel_Name']); t=tot[k]; t[0]+=1; t[1]+=we-ws; t[2]+=wu; t[3]+=b['e']-b['s']; t[4]+=ru
+    print('%8.3f %-34s %8.1f %8.1f %8.1f %8.1f  %s'%((b['s']-t0)/1e6,k,(we-ws)/1e3,wu/1e3,(b['e']-b['s'])/1e3,ru/1e3,nm))
+print('per step: %-26s %4s %9s %9s %9s %9s'%('kernel','n','wait ms','under','run ms','under'))
+for k,t in sorted(tot.items()): print('          %-26s %4d %9.3f %9.3f %9.3f %9.3f'%(k[:26],t[0],t[1]/1e6,t[2]/1e6,t[3]/1e6,t[4]/1e6))
+t=[sum(v[i] for v in tot.values()) for i in range(5)]
+print('          %-26s %4d %9.3f %9.3f %9.3f %9.3f'%('all bn_bwd',t[0],t[1]/1e6,t[2]/1e6,t[3]/1e6,t[4]/1e6))
+print('side-queue wgrad kernels: n %d sum %.3f ms union %.3f ms'%(len(side),sum(w['e']-w['s'] for w in side)/1e6,(union(side) if side else 0)/1e6))
