@@ -49,7 +49,8 @@ const char* dcn_version(void);
  * DCN_GEMM_UNI, DCN_GEMM_SK_FIXUP, DCN_BN_BWD_FUSED, DCN_DEFER_RESIDUAL_ADD, DCN_WGRAD_TILE, DCN_WGRAD_DEEP, DCN_WGRAD_ROLES,
  * DCN_WGRAD_SPLITS, DCN_GEMM_HL, DCN_HL_MIN_K, DCN_GEMM_HL_ROWS, DCN_WGRAD_HL, DCN_HL_PRODUCERS, DCN_HL_ONLY_MID, DCN_STEM_POOL_FUSED, DCN_BN_REVERSE, DCN_BN_NT, DCN_BN_REDUCE_WIDE, DCN_WSPLIT_OVERLAP,
  * DCN_BN_BWD_LEAN (0: the batch-norm backward kernels never run their <= 48-VGPR instances beside the side stream's weight-gradient
- * GEMMs), DCN_BN_BWD_LEAN_MASK (which of them do: 1 reduce, 2 finalize, 4 blocked apply) -- are read ONCE, at the first call that needs them -- never on the
+ * GEMMs), DCN_BN_BWD_LEAN_MASK (which of them do: 1 reduce, 2 finalize, 4 blocked apply), DCN_BN_BWD_LEAN_DEPTH (rows in flight per
+ * work-item of that blocked apply instance: 1, 2 or 3) -- are read ONCE, at the first call that needs them -- never on the
  * launch path.  dcn_reload_env re-reads them (tests / tuning scripts that change a variable in-process); not to be called
  * while another thread is inside the library. */
 void dcn_reload_env(void);

@@ -22,6 +22,14 @@
 #define DCN_MAX_VGPRS(n) __attribute__((amdgpu_num_vgpr(n)))
 #endif
 
+// The optimiser forgets what it knew about a UNIFORM integer (kept in a scalar register): nothing computed from it is hoisted
+// out of a loop into registers that then stay occupied across it.
+#if defined(DCN_HOSTEMU_BUILD)
+#define DCN_OPAQUE_UNIFORM(v) ((void)(v))
+#else
+#define DCN_OPAQUE_UNIFORM(v) asm volatile("" : "+s"(v))
+#endif
+
 // Nothing is scheduled across this point: neither by the instruction scheduler nor (memory accesses) by the passes in front of it.
 #define DCN_SCHED_FENCE() do { asm volatile("" ::: "memory"); __builtin_amdgcn_sched_barrier(0); } while (0)
 

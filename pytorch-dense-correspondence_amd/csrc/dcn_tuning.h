@@ -73,6 +73,11 @@
 //                           instead of queueing behind its round.  The stand-alone dcn_bn_backward* calls follow the two switches
 //                           alone.  Same results bit for bit.
 //   DCN_BN_BWD_LEAN_MASK    which kernels DCN_BN_BWD_LEAN covers: 1 the reduction, 2 finalize, 4 the blocked apply pass (default 7)
+//   DCN_BN_BWD_LEAN_DEPTH   rows of the streamed operands a work-item of the lean blocked apply pass keeps in flight.  1: the one-row
+//                           instances.  2: two rows.  3 (default): three where the pass writes no pixel-blocked image and the
+//                           upstream gradient is one tensor, two everywhere else.  Beside the GEMM a CU holds one such workgroup,
+//                           so with one row the pass is bound by latency, not by HBM.  Same results bit for bit.  (The reduction
+//                           and finalize have one-row lean instances only.)
 #pragma once
 
 namespace dcn {
@@ -117,6 +122,7 @@ struct Tuning {
     int bn_reverse = 0;          // see DCN_BN_REVERSE above
     int bn_bwd_lean = 1;         // see DCN_BN_BWD_LEAN above
     int bn_bwd_lean_mask = 7;    // see DCN_BN_BWD_LEAN_MASK above
+    int bn_bwd_lean_depth = 3;   // see DCN_BN_BWD_LEAN_DEPTH above
     int wgrad_roles = 1;         // wide tile: wavefronts 0-3 stage the activations, 4-7 the gradient (0: copy spread over all 8)
 };
 

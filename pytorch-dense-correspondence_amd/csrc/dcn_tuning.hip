@@ -72,6 +72,7 @@ void read_env(Tuning& t) {
     if (const char* e = getenv("DCN_BN_REDUCE_WIDE")) t.bn_reduce_wide = atoi(e);
     if (const char* e = getenv("DCN_BN_BWD_LEAN")) t.bn_bwd_lean = atoi(e) != 0;
     if (const char* e = getenv("DCN_BN_BWD_LEAN_MASK")) t.bn_bwd_lean_mask = atoi(e) & 7;
+    if (const char* e = getenv("DCN_BN_BWD_LEAN_DEPTH")) { const int v = atoi(e); t.bn_bwd_lean_depth = v < 1 ? 1 : (v > 3 ? 3 : v); }
 }
 
 }  // namespace

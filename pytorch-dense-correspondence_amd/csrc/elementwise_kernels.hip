@@ -683,6 +683,168 @@ bn_bwd_apply_blocked_kernel(DCN_BN_APB_ARGS) { bn_bwd_apply_blocked_body<false, 
 template <bool DQ>   // (DQ false: dq is null -- the 4 x 4 block of the pixel-blocked image is not kept)
 __global__ void __launch_bounds__(256) DCN_MAX_VGPRS(48)
 bn_bwd_apply_blocked_lean_kernel(DCN_BN_APB_ARGS) { bn_bwd_apply_blocked_body<true, DQ>(DCN_BN_APB_PASS); }
+
+// DEEP (the blocked apply pass, DCN_BN_BWD_LEAN_DEPTH): the lean budget again -- beside the GEMM a CU holds ONE such workgroup,
+// one wavefront per SIMD, and with one row in flight per work-item the pass was bound by latency, not by HBM (about 2 KB in
+// flight per wavefront) -- with SEVERAL rows of the streamed operands requested before the oldest is used.  What pays for the
+// rows' registers: one 32-bit offset from uniform bases; the per-channel constants come from LDS (lgkmcnt), because a global
+// load waited for behind the rows in flight would drain them all (vmcnt counts in order); one body per combination of the
+// optional inputs AND outputs.  The ReLU mask is the byte mask here: a call that passes the activation instead takes the lean
+// instance.  (The reduction has no such instance: with two rows in flight its sixteen accumulators and the statistics do not fit,
+// and keeping the maxima and the statistics in LDS put four dependent LDS round trips into every row -- 2.4 x slower beside the
+// GEMM, profiles/EXPERIMENTS.md.)
+struct BnBwdRow { float4 g, h, v; unsigned m; };
+__device__ __forceinline__ const float* bn_at(const float* p, unsigned bytes) {
+    return reinterpret_cast<const float*>(reinterpret_cast<const char*>(p) + bytes);
+}
+// the requests of one row: float4 number o (a 32-bit index from the uniform bases)
+template <bool DY2, bool MASK>
+__device__ __forceinline__ void bn_bwd_row_issue(BnBwdRow& w, const float* x_b, const float* dy_b, const float* dy2_b,
+                                                 const unsigned char* mask_b, unsigned o) {
+    w.v = *reinterpret_cast<const float4*>(bn_at(x_b, 16u * o));
+    w.g = *reinterpret_cast<const float4*>(bn_at(dy_b, 16u * o));
+    if (DY2) w.h = *reinterpret_cast<const float4*>(bn_at(dy2_b, 16u * o));
+    if (MASK) w.m = mask_b[o];
+}
+// ... and its upstream gradient once they have arrived: load_dy and relu_masked, operation for operation
+template <bool DY2, bool MASK>
+__device__ __forceinline__ float4 bn_bwd_row_grad(const BnBwdRow& w) {
+    float4 g = w.g;
+    if (DY2) { g.x += w.h.x; g.y += w.h.y; g.z += w.h.z; g.w += w.h.w; }
+    if (MASK) {
+        const unsigned m = w.m;
+        g.x = (m & 1u) ? g.x : 0.f; g.y = (m & 2u) ? g.y : 0.f; g.z = (m & 4u) ? g.z : 0.f; g.w = (m & 8u) ? g.w : 0.f;
+    }
+    return g;
+}
+#define DCN_OPAQUE_F4(v) do { DCN_OPAQUE_INT(v.x); DCN_OPAQUE_INT(v.y); DCN_OPAQUE_INT(v.z); DCN_OPAQUE_INT(v.w); } while (0)
+// The pass with D rows of a work-item's pixel quad in flight -- row r + D is requested behind row r's stores.  The five per-channel
+// constants of both groups are staged in LDS once per workgroup (20 KB) and read back one at a time, each where the expression
+// a * ((g - b) - (((v - mu) * is) * d))  uses it.
+// One call is one workgroup's 256 work-items from j0 on, addressed from its first quad (uniform 64-bit bases, 32-bit offsets).
+// The waits between the rows are counted ones only in straight-line code -- a branch around a store makes the compiler assume the
+// store away and wait for everything older -- so GUARD = false (every work-item and every row of the workgroup exists) is
+// instantiated per combination of the OUTPUTS as well (GOUT / DX / HL: 0 absent, 1 present, 2 look at the pointer); the one or
+// two workgroups at the end of the tensor take GUARD = true (one row at a time where dy2 is added and the 4 x 4 block is kept:
+// it did not fit).  `rev` and `nt` are ignored by these instances.
+constexpr int kBnDeepPitch = 2 * 128;   // float4 per plane of the staged constants: two groups of up to 512 channels
+template <int D, bool DQ, bool DY2, bool MASK, int GOUT, int DX, int HL, bool GUARD>
+__device__ __forceinline__ void
+bn_bwd_apply_deep_body(int64_t j0, const float* __restrict__ dy, const float* dy2, const unsigned char* __restrict__ relu_mask,
+                       const float* __restrict__ x, float* __restrict__ dx, float* g_out, dcnsplit::u32x4* __restrict__ dq,
+                       float s, int c4n, int64_t rows, int64_t rows_per_group, dcnsplit::u32x2* __restrict__ hl, const float4* s_k) {
+    DCN_OPAQUE_UNIFORM(c4n);   // (the reciprocal of the divisions below is formed here, not kept in a register across the rounds)
+    const unsigned uc4n = (unsigned)c4n;
+    const int64_t q0 = j0 / c4n;                // the workgroup's first pixel quad, its first float4, the rows from there on
+    const int64_t eb = q0 * 4 * c4n;
+    const int64_t left = rows - q0 * 4, gleft = rows_per_group - q0 * 4, live_n = ((rows + 3) >> 2) * c4n - q0 * c4n;
+    const unsigned nrow = left < (1 << 20) ? (unsigned)left : (1u << 20);
+    const unsigned grow = gleft <= 0 ? 0u : (gleft < (1 << 20) ? (unsigned)gleft : (1u << 20));   // rows of the first group among them
+    const unsigned nlive = live_n < (1 << 20) ? (unsigned)live_n : (1u << 20);
+    const unsigned lim = nrow * uc4n - 1u;      // the last float4 there is, from eb
+    const float* x_b = x + eb * 4;
+    const float* dy_b = dy + eb * 4;
+    const float* dy2_b = DY2 ? dy2 + eb * 4 : dy2;
+    const unsigned char* mask_b = MASK ? relu_mask + eb : relu_mask;
+    const unsigned rel = (unsigned)(j0 - q0 * c4n) + threadIdx.x;
+    const unsigned qr = rel / uc4n, cq = rel - qr * uc4n;
+    unsigned er = qr * 4u * uc4n + cq;                                          // float4 of row 0, from eb
+    unsigned sec = qr * 4u >= grow ? 1u : 0u;
+    DCN_OPAQUE_INT(sec);
+    unsigned ks = (sec << 7) + cq;                                              // this work-item's constants in s_k
+    unsigned row0 = qr * 4u, rows_l = rel < nlive ? nrow : 0u;                  // (a work-item past the end stores nothing)
+    DCN_OPAQUE_INT(er); DCN_OPAQUE_INT(ks);
+    if (GUARD) { DCN_OPAQUE_INT(row0); DCN_OPAQUE_INT(rows_l); }
+    const float4* kp = s_k + ks;
+    BnBwdRow w[4];
+    float o[4][4];
+    auto issue = [&](int r) {
+        const unsigned e = er + (unsigned)r * uc4n;
+        bn_bwd_row_issue<DY2, MASK>(w[r], x_b, dy_b, dy2_b, mask_b, GUARD ? (e < lim ? e : lim) : e);
+    };
+#pragma unroll
+    for (int r = 0; r < D; ++r) issue(r);
+    DCN_SCHED_FENCE();
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        float4 g = bn_bwd_row_grad<DY2, MASK>(w[r]);
+        float4 t = w[r].v, u, k;
+        DCN_OPAQUE_F4(g); DCN_OPAQUE_F4(t);
+        k = kp[0];                 t = make_float4(t.x - k.x, t.y - k.y, t.z - k.z, t.w - k.w); DCN_OPAQUE_F4(t); DCN_SCHED_FENCE();
+        k = kp[kBnDeepPitch];      t = make_float4(t.x * k.x, t.y * k.y, t.z * k.z, t.w * k.w); DCN_OPAQUE_F4(t); DCN_SCHED_FENCE();
+        k = kp[2 * kBnDeepPitch];  t = make_float4(t.x * k.x, t.y * k.y, t.z * k.z, t.w * k.w); DCN_OPAQUE_F4(t); DCN_SCHED_FENCE();
+        k = kp[3 * kBnDeepPitch];  u = make_float4(g.x - k.x, g.y - k.y, g.z - k.z, g.w - k.w); DCN_OPAQUE_F4(u); DCN_SCHED_FENCE();
+        k = kp[4 * kBnDeepPitch];
+        t = make_float4(k.x * (u.x - t.x), k.y * (u.y - t.y), k.z * (u.z - t.z), k.w * (u.w - t.w)); DCN_OPAQUE_F4(t);
+        const bool in = !GUARD || row0 + (unsigned)r < rows_l;
+        if (DQ) {
+            o[r][0] = in ? t.x : 0.f; o[r][1] = in ? t.y : 0.f; o[r][2] = in ? t.z : 0.f; o[r][3] = in ? t.w : 0.f;
+        }
+        if (in) {
+            unsigned e = er;       // (formed again from the one register: no offset per row in flight is kept for the stores)
+            DCN_OPAQUE_INT(e);
+            e += (unsigned)r * uc4n;
+            if (DX == 1 || (DX == 2 && dx)) *reinterpret_cast<float4*>(const_cast<float*>(bn_at(dx + eb * 4, 16u * e))) = t;
+            if (GOUT == 1 || (GOUT == 2 && g_out)) *reinterpret_cast<float4*>(const_cast<float*>(bn_at(g_out + eb * 4, 16u * e))) = g;
+            if (HL == 1 || (HL == 2 && hl)) {   // (eb is a multiple of 8 float4: c4n % 8 == 0 where there is an hl32 image)
+                __builtin_amdgcn_sched_barrier(0);   // (behind the two stores above: g is dead, and the halves of split4 one by one)
+                dcnsplit::h2 a0, b0, a1, b1;
+                dcnsplit::split2(t.x * s, t.y * s, a0, b0);
+                __builtin_amdgcn_sched_barrier(0);
+                dcnsplit::split2(t.z * s, t.w * s, a1, b1);
+                const dcnsplit::h4 ha = {a0[0], a0[1], a1[0], a1[1]}, hb = {b0[0], b0[1], b1[0], b1[1]};
+                dcnsplit::u32x2* line = reinterpret_cast<dcnsplit::u32x2*>(reinterpret_cast<char*>(hl + (eb >> 3) * 16) +
+                                                                             8u * ((e >> 3) * 16u + (e & 7u)));
+                line[0] = __builtin_bit_cast(dcnsplit::u32x2, ha);
+                line[8] = __builtin_bit_cast(dcnsplit::u32x2, hb);
+            }
+        }
+        if (DQ) { DCN_OPAQUE_INT(o[r][0]); DCN_OPAQUE_INT(o[r][1]); DCN_OPAQUE_INT(o[r][2]); DCN_OPAQUE_INT(o[r][3]); }   // (the row itself is kept, nothing derived from it)
+        DCN_SCHED_FENCE();
+        if (r + D < 4) { issue(r + D); DCN_SCHED_FENCE(); }
+    }
+    if (DQ && dq && (!GUARD || row0 < rows_l))   // (null: the weight gradient reads the hl32 image)
+        dcnsplit::store_blocked_quad(reinterpret_cast<dcnsplit::u32x4*>(reinterpret_cast<char*>(dq + eb) + 16u * er), 0, 0, c4n, o, s);
+}
+// (D: rows in flight where the upstream gradient is one tensor; two where dy2 is added.  DQ false: there is an hl32 image.)
+template <int D, bool DQ>
+__global__ void __launch_bounds__(256) DCN_MAX_VGPRS(48)
+bn_bwd_apply_blocked_deep_kernel(DCN_BN_APB_ARGS) {
+    __shared__ float4 s_k[5 * kBnDeepPitch];   // [mean, invstd, k3, k2, k1][group][channel quad]
+    const int ng = rows_per_group < rows ? 2 : 1;
+    for (int i = threadIdx.x; i < ng * 5 * c4n; i += 256) {
+        const int g = i / (5 * c4n), n = (i - g * 5 * c4n) / c4n, cq = i - (g * 5 + n) * c4n;
+        const float* src = n == 0 ? mean + g * gstride : (n == 1 ? invstd + g * gstride : ((n == 2 ? k3 : (n == 3 ? k2 : k1)) + g * kstride));
+        s_k[n * kBnDeepPitch + g * 128 + cq] = *reinterpret_cast<const float4*>(src + 4 * cq);
+    }
+    __syncthreads();
+    // (uniform; said so, for a scalar register)
+    const float s = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, dcnsplit::pow2_scale(*absmax))));
+    const int64_t total = ((rows + 3) >> 2) * c4n;
+    for (int64_t j0 = (int64_t)blockIdx.x * 256; j0 < total; j0 += (int64_t)gridDim.x * 256) {   // (uniform)
+        // every work-item of this round has a quad, and the last of them all four rows of it
+        const bool whole = j0 + 256 <= total && ((j0 + 255) / c4n) * 4 + 3 < rows;
+#define DCN_BN_DEEP(DD, DY2, MASK, GOUT, DX, HL, GUARD)                                                                        \
+        bn_bwd_apply_deep_body<DD, DQ, DY2, MASK, GOUT, DX, HL, GUARD>(j0, dy, dy2, relu_mask, x, dx, g_out, dq, s, c4n, rows,  \
+                                                                       rows_per_group, hl, s_k)
+#define DCN_BN_DEEP_DX(DD, DY2, MASK, HL)                                                                                      \
+        do {                                                                                                                   \
+            if (g_out) { if (dx) DCN_BN_DEEP(DD, DY2, MASK, 1, 1, HL, false); else DCN_BN_DEEP(DD, DY2, MASK, 1, 0, HL, false); } \
+            else { if (dx) DCN_BN_DEEP(DD, DY2, MASK, 0, 1, HL, false); else DCN_BN_DEEP(DD, DY2, MASK, 0, 0, HL, false); }     \
+        } while (0)
+#define DCN_BN_DEEP_OUT(DD, DY2, MASK)                                                                                         \
+        do {                                                                                                                   \
+            if (!whole) DCN_BN_DEEP(((DQ && DY2) ? 1 : DD), DY2, MASK, 2, 2, 2, true);                                                            \
+            else if (DQ && !hl) DCN_BN_DEEP_DX(DD, DY2, MASK, 0);                                                              \
+            else DCN_BN_DEEP_DX(DD, DY2, MASK, 1);                                                                             \
+        } while (0)
+        if (relu_mask) { if (dy2) DCN_BN_DEEP_OUT(2, true, true); else DCN_BN_DEEP_OUT(D, false, true); }
+        else { if (dy2) DCN_BN_DEEP_OUT(2, true, false); else DCN_BN_DEEP_OUT(D, false, false); }
+#undef DCN_BN_DEEP_OUT
+#undef DCN_BN_DEEP_DX
+#undef DCN_BN_DEEP
+    }
+}
 #undef DCN_BN_APB_ARGS
 #undef DCN_BN_APB_PASS
 
@@ -993,6 +1155,10 @@ void launch_bn_bwd(const float* dy, const float* relu_out, const unsigned char* 
     const float* mean = stats + 2 * C;
     const float* invstd = stats + 3 * C;
     int chunks = reduced_tiles_per_group;
+    // DCN_BN_BWD_LEAN_DEPTH: where the lean blocked apply pass would run, the one with several rows in flight (it takes the ReLU
+    // mask as bytes or not at all, and keeps the constants of at most two groups of 512 channels in LDS)
+    const int depth = tuning().bn_bwd_lean_depth;
+    const bool deep = depth > 1 && !(relu_out && !relu_mask);
     // bytes per element read by both streaming passes: dy (+ dy2), x, the ReLU mask byte per float4 (or the activation)
     const double in_bytes = 8.0 + (dy2 ? 4.0 : 0.0) + (relu_mask ? 0.25 : (relu_out ? 4.0 : 0.0));
     if (chunks <= 0) {
@@ -1025,8 +1191,11 @@ void launch_bn_bwd(const float* dy, const float* relu_out, const unsigned char* 
         const bool hl = hl_dx && (C % 32) == 0;
         ObservedLaunch obs(DCN_PROF_BN_BWD_APPLY, (double)rows * C * (in_bytes + ((hl && !keep_dx) ? 0.0 : 4.0) + (g_out ? 4.0 : 0.0) +
                                                                       (dq ? 4.0 : 0.0) + (hl ? 4.0 : 0.0)), st);
+        const bool deep_apply = deep && C <= 512 && groups <= 2;
         const auto kernel = !(lean & 4) ? bn_bwd_apply_blocked_kernel
-                                        : (dq ? bn_bwd_apply_blocked_lean_kernel<true> : bn_bwd_apply_blocked_lean_kernel<false>);
+                            : (!deep_apply ? (dq ? bn_bwd_apply_blocked_lean_kernel<true> : bn_bwd_apply_blocked_lean_kernel<false>)
+                               : (dq ? bn_bwd_apply_blocked_deep_kernel<2, true>
+                                     : (depth > 2 ? bn_bwd_apply_blocked_deep_kernel<3, false> : bn_bwd_apply_blocked_deep_kernel<2, false>)));
         hipLaunchKernelGGL(kernel, dim3(blocks_for(((rows + 3) / 4) * (C / 4), kGridCap)), dim3(256), 0, st,
                            dy, dy2, relu_out, relu_mask, x, mean, invstd, (const float*)k123, (const float*)(k123 + C),
                            (const float*)(k123 + 2 * C), (hl_dx && (C % 32) == 0 && !keep_dx) ? nullptr : dx, g_out,
