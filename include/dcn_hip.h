@@ -797,6 +797,51 @@ int dcn_concat_samples(int groups, const int* n, const int64_t* const* idx_a, co
                        void* stream);
 
 /* =====================================================================================================
+ * 9a. SYNTHETIC_MULTI_OBJECT training samples -- replaces, for device-resident frames, the whole of
+ *     get_synthetic_multi_object_within_scene_data (dense_correspondence/dataset/spartan_dataset_masked.py:890-1053): two
+ *     within-scene match searches (object a: frames a1 -> a2, object b: b1 -> b2), the occlusion prune and concatenation of
+ *     section 8, the non-matches of section 9 on the merged frame-2 mask, and the merged images.  One chain on the caller's
+ *     stream, no host synchronisation; the per-object non-matches of a composition of the section 9 entries are never built.
+ *     n samples (1 <= n <= 1024) of [h][w] frames in the slot order of dcn_gather_frames(k = 4) -- a1, a2, b1, b2:
+ *       depth uint16 [4][n][h][w] millimetres; mask uint8 [4][n][h][w], 0 / 1; rgb uint8 [4][n][h][w][3], or NULL: no images
+ *       are written (net_* / mask_* must then be NULL); cams float [2][n][DCN_SAMPLE_CAM_FLOATS], row 0 for a1 -> a2, row 1
+ *       for b1 -> b2; foreground int32 [n][2], the records of section 8; empty_in uint8 [n] or NULL: a sample marked here
+ *       (its frames could not be chosen) reads no random number and comes out empty; mean, std: HOST float [3] (with rgb).
+ *     Recipe per sample: (:906-927) the match search of dcn_within_scene_samples for object a and for object b on the
+ *     unaugmented frames -- `attempts` candidates each, from mask a1 / b1 (DCN_SAMPLE_ONLY_OFF_MASK) or uniform, survivors in
+ *     candidate order, frame-2 coordinates truncated like `.long()`; this type has no rotation and no background
+ *     randomization.  (:929-955) the rule of dcn_merge_prune with DCN_MERGE_DROP_EMPTY: an entry of the object behind is
+ *     dropped when its frame-1 or its frame-2 pixel lies inside the front object's mask of that frame; a's kept entries, then
+ *     b's.  The sample is empty (type -1, no entries) when a's or b's search finds nothing or a's or b's list is pruned to
+ *     nothing.  (:957-1000) on the merged frame-2 mask clip(mask a2 + mask b2, 0, 1): k_masked non-matches per match from its
+ *     pixels (uniform over the image when it is empty), k_background from its inverse (DCN_SAMPLE_MASK_INV) or uniform, in
+ *     the layout and with the `pick` rule of dcn_complete_samples.  The blind list is EMPTY (:1053 returns empty tensors).
+ *     Images (rgb != NULL): net_1, net_2, mask_1, mask_2 exactly as dcn_merge_images writes them (each may be NULL).
+ *     Outputs as in section 9: idx_a / idx_b int64 [capacity] (16-byte aligned, -1 from offsets[4n] on), offsets [4n + 1],
+ *     empty [n], type [n] = DCN_SYNTHETIC_DATA_TYPE or -1, status [1] = DCN_SAMPLE_BAD_* bits (written, not accumulated).
+ *       capacity = n * 2 * attempts * (1 + k_masked + k_background)
+ *     Random numbers: seeds [n] (the hash of (seed, site, k) of section 9) or, seeds == NULL, the replay streams rand /
+ *     rand_offsets[s * (n + 1) + p] over THIS entry's DCN_SYNTHETIC_SITES sites: CAND_A and CAND_B read A values (from the
+ *     mask) or 2A (uniform: all u, then all v); MASKED k_masked * M or 2 k_masked * M when uniform (M = the merged match count);
+ *     BACKGROUND likewise.  A stream shorter than its site needs reads 0 there and raises DCN_SAMPLE_BAD_DRAWS -- except
+ *     CAND_B of a sample whose object a search found nothing: the reference never searches b's scene then, so the stream may
+ *     be absent.  workspace: device, dcn_synthetic_workspace(n, h, w, attempts) bytes (0: sizes outside the contract).
+ * ===================================================================================================== */
+#define DCN_SYNTHETIC_DATA_TYPE 4
+#define DCN_SYNTHETIC_SITES 4
+#define DCN_SYNTHETIC_SITE_CAND_A 0
+#define DCN_SYNTHETIC_SITE_CAND_B 1
+#define DCN_SYNTHETIC_SITE_MASKED 2
+#define DCN_SYNTHETIC_SITE_BACKGROUND 3
+size_t dcn_synthetic_workspace(int n, int h, int w, int64_t attempts);
+int dcn_synthetic_samples(int n, int h, int w, const uint16_t* depth, const uint8_t* mask, const uint8_t* rgb,
+                          const float* cams, int64_t attempts, int k_masked, int k_background, int flags,
+                          const int32_t* foreground, const uint8_t* empty_in, const int64_t* seeds, const float* rand,
+                          const int64_t* rand_offsets, const float* mean, const float* std, float* net_1, float* net_2,
+                          float* mask_1, float* mask_2, int64_t* idx_a, int64_t* idx_b, int64_t capacity, int64_t* offsets,
+                          uint8_t* empty, int32_t* type, int32_t* status, void* workspace, void* stream);
+
+/* =====================================================================================================
  * 10. Frame store -- replaces, for frames kept in device memory, the frame choice of the reference's loader
  *     (dense_correspondence/dataset/spartan_dataset_masked.py: the five type wrappers :543-575, :860-905 and the helpers
  *     get_random_image_index :408-420, get_random_single_object_scene_name :442-451, get_different_scene_for_object

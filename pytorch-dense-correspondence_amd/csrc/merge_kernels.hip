@@ -20,6 +20,7 @@
 //                        per-chunk LDS table of wave counts), fills the unused tail with -1 and writes offsets / empty / status.
 #include "dcn_common.h"
 #include "image_norm.h"
+#include "merge_rules.h"
 
 namespace {
 
@@ -181,7 +182,7 @@ __global__ void __launch_bounds__(kPruneThreads) prune_count_kernel(PruneArgs a)
     const unsigned char* occ[2];
     for (int f = 0; f < 2; ++f) {
         const unsigned char* m = a.mask[f][1 - o];
-        const bool other_in_front = (a.fg[2 * s + f] == DCN_MERGE_FG_B) == (o == 0);
+        const bool other_in_front = dcn::other_in_front(a.fg, s, f, o);
         chk[f] = m != nullptr;
         occ[f] = (m && other_in_front) ? m + (size_t)s * hw : nullptr;
     }

@@ -206,6 +206,9 @@ SYMBOLS = {
                              + [c_int, c_void_p, c_void_p, c_int64] + [c_void_p] * 6),
     "dcn_across_scene_samples": (c_int, [c_int, c_int, c_int, c_void_p, c_void_p, c_int64] + [c_void_p] * 4
                                  + [c_int, c_void_p, c_void_p, c_int64] + [c_void_p] * 6),
+    "dcn_synthetic_workspace": (c_size_t, [c_int, c_int, c_int, c_int64]),
+    "dcn_synthetic_samples": (c_int, [c_int, c_int, c_int] + [c_void_p] * 4 + [c_int64, c_int, c_int, c_int] + [c_void_p] * 13
+                              + [c_int64] + [c_void_p] * 6),
     "dcn_concat_samples": (c_int, [c_int] + [c_void_p] * 8 + [c_int64, c_void_p, c_void_p, c_void_p]),
     "dcn_merge_prune": (c_int, [c_int, c_int, c_int] + [c_void_p] * 10 + [c_int64] + [c_void_p] * 5 + [c_int64, c_int]
                         + [c_void_p] * 9),

@@ -17,8 +17,8 @@ import torch
 
 from . import _args, _lib
 from .samples import (CAM_FLOATS, DIFFERENT_OBJECT, MULTI_OBJECT, SINGLE_OBJECT_ACROSS_SCENE, SINGLE_OBJECT_WITHIN_SCENE,
-                      SYNTHETIC_MULTI_OBJECT, build_across_scene_samples, build_within_scene_samples, concat_sample_batches,
-                      options_from_config)
+                      SYNTHETIC_MULTI_OBJECT, build_across_scene_samples, build_synthetic_multi_object_samples,
+                      build_within_scene_samples, concat_sample_batches, options_from_config)
 
 BAD_INDEX, BAD_DRAWS, NO_CANDIDATES = 1, 2, 4
 SLOTS = 4
@@ -278,6 +278,13 @@ def data_type_distribution(training_config):
 
 
 def _build_samples(fb, dt, o, generator):
+    if dt == SYNTHETIC_MULTI_OBJECT:
+        return build_synthetic_multi_object_samples(
+            fb.depth, fb.mask, fb.cams, fb.rgb, num_matching_attempts=o.num_matching_attempts,
+            sample_matches_only_off_mask=o.sample_matches_only_off_mask,
+            num_masked_non_matches_per_match=o.num_masked_non_matches_per_match,
+            num_background_non_matches_per_match=o.num_background_non_matches_per_match,
+            use_image_b_mask_inv=o.use_image_b_mask_inv, generator=generator, empty=fb.empty)[0]
     if dt in (SINGLE_OBJECT_WITHIN_SCENE, MULTI_OBJECT):
         return build_within_scene_samples(fb.depth[0], fb.depth[1], fb.mask[0], fb.mask[1], None, None, None, fb.rgb[0],
                                           fb.rgb[1], num_matching_attempts=o.num_matching_attempts,
@@ -290,13 +297,19 @@ def _build_samples(fb, dt, o, generator):
                                       domain_randomize=o.domain_randomize, generator=generator, data_type=dt)
 
 
-def draw_training_batch(store, batch_size, training_config, *, generator=None, host_rng=None, per_pair_types=False):
+def draw_training_batch(store, batch_size, training_config, *, generator=None, host_rng=None, per_pair_types=False,
+                        synthetic_multi_object=False):
     """One training batch from the store: the data type drawn on the host (``host_rng``: a numpy RandomState / Generator,
     default ``np.random``) from training.yaml's probabilities -- one type per batch, since the loss composes per call --
     then select_frames and build_within_scene_samples / build_across_scene_samples with options_from_config, all with
     ``generator``.  -> (SampleBatch, data_type, FrameBatch).  No host synchronization (SampleBatch.pair_lists() is the one
-    read).  SYNTHETIC_MULTI_OBJECT (select_frames serves its four frames for merge.merge_synthetic_samples) is not chained
-    here: a probability > 0 for it raises NotImplementedError.
+    read).
+
+    ``synthetic_multi_object``: False (the default) keeps SYNTHETIC_MULTI_OBJECT out of this function: a probability > 0 for
+    it raises NotImplementedError.  True draws it like any other type: select_frames gathers its four frames (a1, a2, b1, b2)
+    and samples.build_synthetic_multi_object_samples builds the samples, with ``FrameBatch.empty`` passed on; the
+    SampleBatch's inputs are the merged images, its BLIND lists are empty (the reference returns none for this type) and its
+    ``aug_params`` is None (the type is not augmented; joined with other types, the joined batch's ``aug_params`` is None too).
 
     ``per_pair_types=True``: one type per PAIR, as the reference's loader draws one per sample -- ``batch_size`` draws of
     ``host_rng.choice`` in pair order; the pairs of each drawn type go through select_frames and their builder as one group
@@ -305,9 +318,10 @@ def draw_training_batch(store, batch_size, training_config, *, generator=None, h
     [batch_size] in draw order, [FrameBatch per group]) for ``loss_composer.get_loss_mixed(..., sb.device_lists())``; no host
     synchronization."""
     types, ps = data_type_distribution(training_config)
-    if SYNTHETIC_MULTI_OBJECT in types:
+    if SYNTHETIC_MULTI_OBJECT in types and not synthetic_multi_object:
         raise NotImplementedError("draw_training_batch does not build SYNTHETIC_MULTI_OBJECT samples: select its four frames "
-                                  "with select_frames and merge them with merge.merge_synthetic_samples")
+                                  "with select_frames and merge them with merge.merge_synthetic_samples, or pass "
+                                  "synthetic_multi_object=True")
     for t in types:
         store.check_type(t)
     rng = host_rng if host_rng is not None else np.random

@@ -8,7 +8,10 @@ uniform), the reprojection test of ``batch_find_pixel_correspondences`` on the u
 matches), then on the rotated masks the masked / background non-matches (``create_non_correspondences`` +
 ``create_non_matches``) and the blind non-matches.  A pair whose mask a is empty (with ``sample_matches_only_off_mask``) or
 where no match survives is empty: type -1 and no entries, as ``return_empty_data``.  Across-scene (SINGLE_OBJECT_ACROSS_SCENE,
-DIFFERENT_OBJECT): ``cross_scene_num_samples`` pixels of each mask, rotated, in the blind slot.
+DIFFERENT_OBJECT): ``cross_scene_num_samples`` pixels of each mask, rotated, in the blind slot.  SYNTHETIC_MULTI_OBJECT
+(get_synthetic_multi_object_within_scene_data :890-1053, csrc/synthetic_kernels.hip): ``build_synthetic_multi_object_samples``
+runs both objects' match searches, the occlusion prune, the non-matches on the merged frame-2 mask and the image merge as one
+chain; this type has no augmentation and its blind list is empty.
 
 Masks are 0/1 (uint8, or anything ``.to(uint8)`` maps onto 0/1); other values are outside the contract (include/dcn_hip.h
 section 9).  Random numbers are drawn with the caller's generator into per-pair 64-bit seeds (the kernels hash them), or the
@@ -28,6 +31,7 @@ ONLY_OFF_MASK, MASK_INV = 1, 2
 BAD_INDEX, BAD_DRAWS, BAD_OFFSETS = 1, 2, 4
 CONCAT_MAX_GROUPS = 8
 SITES = ("cand", "masked", "background", "blind", "across_a", "across_b")
+SYNTHETIC_SITES = ("cand_a", "cand_b", "masked", "background")      # build_synthetic_multi_object_samples' own streams
 CAM_FLOATS = _args.CAM_FLOATS
 SINGLE_OBJECT_WITHIN_SCENE, SINGLE_OBJECT_ACROSS_SCENE, DIFFERENT_OBJECT, MULTI_OBJECT, SYNTHETIC_MULTI_OBJECT = 0, 1, 2, 3, 4
 
@@ -108,11 +112,12 @@ def draw_seeds(num_pairs, device, generator=None):
                          dtype=torch.int32).view(torch.int64).view(-1)
 
 
-def pack_draws(draws, n, dev):
+def pack_draws(draws, n, dev, sites=SITES):
     """``draws``: {site: sequence of B 1-D float arrays / tensors (None = no values)} -> (rand float32, rand_offsets int64
-    [SITES][B + 1]) on ``dev``: the replay layout of include/dcn_hip.h section 9."""
+    [sites][B + 1]) on ``dev``: the replay layout of include/dcn_hip.h section 9 (``sites=SYNTHETIC_SITES``: of section 9a,
+    see pack_synthetic_draws)."""
     vals, offs, pos = [], [], 0
-    for site in SITES:
+    for site in sites:
         per = draws.get(site) or [None] * n
         if len(per) != n:
             raise ValueError("draws[%r] needs one entry per pair (%d), got %d" % (site, n, len(per)))
@@ -124,18 +129,25 @@ def pack_draws(draws, n, dev):
             pos += a.size
             row.append(pos)
         offs.append(row)
-    unknown = set(draws) - set(SITES)
+    unknown = set(draws) - set(sites)
     if unknown:
-        raise ValueError("unknown draw sites %s (sites: %s)" % (sorted(unknown), SITES))
+        raise ValueError("unknown draw sites %s (sites: %s)" % (sorted(unknown), sites))
     rand = torch.from_numpy(np.concatenate(vals + [np.zeros(1, np.float32)]))
     return rand.to(dev), torch.tensor(offs, dtype=torch.int64).to(dev)
 
 
-def random_source(n, dev, generator, draws, seeds):
+def pack_synthetic_draws(draws, n, dev):
+    """pack_draws for the four streams of build_synthetic_multi_object_samples: ``cand_a`` / ``cand_b`` (the reference's
+    torch.rand calls of object a's and object b's match search; ``cand_b`` may be None for a sample whose object a search
+    finds nothing), ``masked``, ``background`` -> (rand, rand_offsets int64 [4][B + 1]), include/dcn_hip.h section 9a."""
+    return pack_draws(draws, n, dev, SYNTHETIC_SITES)
+
+
+def random_source(n, dev, generator, draws, seeds, sites=SITES):
     """-> (seeds, rand, rand_offsets): the replay streams of ``draws`` (pack_draws) and no seeds, or per-pair seeds (the
     caller's, or drawn with ``generator``) and no streams."""
     if draws is not None:
-        rand, roff = pack_draws(draws, n, dev)
+        rand, roff = pack_draws(draws, n, dev, sites)
         return None, rand, roff
     return _args.seeds_for(n, dev, generator, seeds), None, None
 
@@ -272,6 +284,78 @@ def complete_samples(uv_a, uv_b, offsets, mask_a, mask_b, *, num_masked_non_matc
                                   _lib.stream_ptr())
     _lib.check(rc, "dcn_complete_samples")
     return _batch(outs, sd, params, max(count, count * k1, count * k2, h * w), count * (1 + k1 + k2) + h * w)
+
+
+def build_synthetic_multi_object_samples(depth, mask, cameras, rgb=None, *, num_matching_attempts,
+                                         sample_matches_only_off_mask, num_masked_non_matches_per_match,
+                                         num_background_non_matches_per_match, use_image_b_mask_inv, generator=None, draws=None,
+                                         seeds=None, foreground=None, empty=None, mean=_aug.DEFAULT_IMAGE_MEAN,
+                                         std=_aug.DEFAULT_IMAGE_STD_DEV):
+    """B SYNTHETIC_MULTI_OBJECT samples on the device (get_synthetic_multi_object_within_scene_data,
+    spartan_dataset_masked.py:890-1053) in one chain: the within-scene match search for object a (frames a1 -> a2) and for
+    object b (b1 -> b2) on the unaugmented frames, the occlusion prune and concatenation of merge.merge_synthetic_samples
+    (a's kept matches, then b's), the masked / background non-matches on the merged frame-2 mask, and the merged images.
+    The per-object non-matches that a composition of build_within_scene_samples would build and drop are never made.
+
+    depth 16-bit [4, B, H, W], mask 0/1 [4, B, H, W], rgb uint8 [4, B, H, W, 3] (optional) in the slot order a1, a2, b1, b2
+    and cameras fp32 [2, B, 50] (row 0: a1 -> a2, row 1: b1 -> b2), as frames.select_frames(...,
+    SYNTHETIC_MULTI_OBJECT) returns them.  ``foreground``: [B, 2] records (merge.FG_A / FG_B per frame) to replay, otherwise
+    merge.draw_foreground(B, device, generator).  ``empty``: bool [B] (FrameBatch.empty), samples that come out empty without
+    reading a random number.  ``draws``: replay streams per site of SYNTHETIC_SITES (pack_synthetic_draws), otherwise
+    per-sample ``seeds`` (drawn with ``generator`` when None).
+
+    -> (SampleBatch, foreground).  input_a / input_b: the merged normalized images of frame 1 / frame 2 and mask_a / mask_b
+    the merged masks as float 0/1 (None without ``rgb``); type 4 or -1; the BLIND list of every sample is EMPTY, as the
+    reference returns empty tensors for it; aug_params None (this type is not augmented); max_list_len / max_pair_len
+    from the capacity B * 2A * (1 + k_masked + k_background).  Twelve launches with images and candidates off the mask; no
+    host synchronization."""
+    from . import merge as _merge
+    lib = _lib.get()
+    if mask is None or mask.dim() != 4 or int(mask.shape[0]) != 4:
+        raise ValueError("mask must be [4, B, H, W] (a1, a2, b1, b2), got %s" % (None if mask is None else tuple(mask.shape),))
+    n, h, w, dev = int(mask.shape[1]), int(mask.shape[2]), int(mask.shape[3]), mask.device
+    if n < 1 or n > 1024:
+        raise ValueError("1 <= B <= 1024 samples per call, got %d" % n)
+    mk = _args.mask(mask.reshape(4 * n, h, w), 4 * n, h, w, "mask")
+    if tuple(depth.shape) != (4, n, h, w):
+        raise ValueError("depth must be 16-bit integer [4, %d, %d, %d], got %s" % (n, h, w, tuple(depth.shape)))
+    dp = _args.depth(depth.reshape(4 * n, h, w), 4 * n, h, w, "depth")
+    if tuple(cameras.shape) != (2, n, CAM_FLOATS):
+        raise ValueError("cameras must be float32 [2, %d, %d], got %s" % (n, CAM_FLOATS, tuple(cameras.shape)))
+    cams = _args.camera_rows(cameras.reshape(2 * n, CAM_FLOATS), 2 * n, "cameras")
+    img = None
+    if rgb is not None:
+        if tuple(rgb.shape) != (4, n, h, w, 3):
+            raise ValueError("rgb must be uint8 [4, %d, %d, %d, 3], got %s" % (n, h, w, tuple(rgb.shape)))
+        img = _args.image(rgb.reshape(4 * n, h, w, 3), 4 * n, h, w, "rgb")
+    A, k1, k2 = int(num_matching_attempts), int(num_masked_non_matches_per_match), int(num_background_non_matches_per_match)
+    if A < 1 or k1 < 1 or k2 < 1:
+        raise ValueError("num_matching_attempts and the non-matches per match must be >= 1")
+    fg = _merge.draw_foreground(n, dev, generator=generator) if foreground is None else _merge._foreground(foreground, n, dev)
+    em = None
+    if empty is not None:
+        if tuple(empty.shape) != (n,):
+            raise ValueError("empty must be [%d], got %s" % (n, tuple(empty.shape)))
+        em = empty.to(torch.bool).contiguous()
+    sd, rand, roff = random_source(n, dev, generator, draws, seeds, SYNTHETIC_SITES)
+    _lib.require_device(dp, mk, img, cams, fg, em, sd, rand, roff)
+    cap = n * 2 * A * (1 + k1 + k2)
+    outs = _outputs(n, cap, dev, lib.dcn_synthetic_workspace(n, h, w, A))
+    idx_a, idx_b, offsets, empty_out, typ, status, ws = outs
+    net = msk = (None, None)
+    m = s = None
+    if img is not None:
+        net = tuple(torch.empty(n, 3, h, w, dtype=torch.float32, device=dev) for _ in range(2))
+        msk = tuple(torch.empty(n, h, w, dtype=torch.float32, device=dev) for _ in range(2))
+        m, s = _args.mean_std(mean), _args.mean_std(std)
+    flags = (ONLY_OFF_MASK if sample_matches_only_off_mask else 0) | (MASK_INV if use_image_b_mask_inv else 0)
+    P = _lib.ptr
+    rc = lib.dcn_synthetic_samples(n, h, w, P(dp), P(mk), P(img), P(cams), A, k1, k2, flags, P(fg), P(em), P(sd), P(rand),
+                                   P(roff), None if m is None else _lib.host_ptr(m), None if s is None else _lib.host_ptr(s),
+                                   P(net[0]), P(net[1]), P(msk[0]), P(msk[1]), P(idx_a), P(idx_b), cap, P(offsets),
+                                   P(empty_out), P(typ), P(status), P(ws), _lib.stream_ptr())
+    _lib.check(rc, "dcn_synthetic_samples")
+    return SampleBatch(net[0], net[1], *outs[:6], sd, None, msk[0], msk[1], 2 * A * max(1, k1, k2), cap // n), fg
 
 
 def _cat(parts):
