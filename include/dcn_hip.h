@@ -1052,6 +1052,13 @@ int dcn_best_match_pairs(int p, int h, int w, int d, const float* res_b, const f
  *     a row past offsets[G].  Outputs and arithmetic are 11b's (the same device functions): columns, is_valid, pred_uv, closer,
  *     row_pair (the row's GROUP, or -1), mask_pixels int32 [G], status int32 [1] (written).  64-bit integer atomics only:
  *     bit-identical from run to run.  No host synchronisation.  1 <= G <= 65535, 1 <= d <= 64, h * w < 2^31.
+ *
+ *     dcn_match_statistics_groups_wide: the same call for groups of MANY rows (the keypoint table, single_image_pair_cross_
+ *     scene_keypoints_quantitative_analysis :1433-1552: an image is searched by (labelled images - 1) * keypoints rows).  The
+ *     search is transposed: a work-item holds one row, a workgroup up to 256 rows of one group and a strip of strip_pixels
+ *     pixels (0: chosen so that the grid fills the device), which pass by all rows through LDS; no cross-lane reduction.  The
+ *     per-(pixel, row) arithmetic is the grouped call's and every accumulation is an integer one, so every output is the
+ *     grouped call's BIT FOR BIT, whatever strip_pixels is.  Same workspace.  strip_pixels >= 0, max_group_rows <= 65535 * 256.
  * ----------------------------------------------------------------------------------------------------- */
 int dcn_reproject_pixels(int v, const struct dcn_frame_store* store, const float* kcam, const int32_t* requests,
                          uint8_t* found, float* u2, float* v2, int32_t* uv, int32_t* status, void* stream);
@@ -1062,6 +1069,12 @@ int dcn_match_statistics_groups(int g, int h, int w, int d, const float* res_b, 
                                 const int64_t* offsets, int64_t max_rows, int max_group_rows, double* columns,
                                 uint8_t* is_valid, int32_t* pred_uv, int32_t* closer, int32_t* row_pair, int32_t* mask_pixels,
                                 int32_t* status, void* workspace, void* stream);
+int dcn_match_statistics_groups_wide(int g, int h, int w, int d, const float* res_b, const uint8_t* mask_b,
+                                     const uint16_t* depth_b, const float* queries, const int64_t* u_a, const int64_t* v_a,
+                                     const uint16_t* depth_q, const float* u_b, const float* v_b, const float* cams,
+                                     const uint8_t* keep, const int64_t* offsets, int64_t max_rows, int max_group_rows,
+                                     int64_t strip_pixels, double* columns, uint8_t* is_valid, int32_t* pred_uv, int32_t* closer,
+                                     int32_t* row_pair, int32_t* mask_pixels, int32_t* status, void* workspace, void* stream);
 
 /* =====================================================================================================
  * 12. Descriptor statistics of a dataset -- replaces, for device-resident descriptor images, the per-image half and the

@@ -12,6 +12,13 @@
 //                       without being copied once per row.  A row with keep == 0 is passed over.
 //                       HBM traffic: G * HW * D * 4 bytes of res_b once, G * HW mask bytes, and R * D query floats per
 //                       workgroup from L2.
+//   wide_stats_kernel   grid (pixel strips, blocks of 256 rows, groups): the same search transposed, for groups of MANY rows
+//                       (the keypoint table: every labelled image is searched by (images - 1) * keypoints rows).  A work-item
+//                       holds one ROW -- its query, ground truth, two keys, two counts, two sums -- and the strip's pixels pass
+//                       by all of them through an LDS tile read at one address by every lane (a broadcast, no bank conflict):
+//                       no shuffle and no barrier in the inner loop, and per row and strip at most one atomic per word.  The
+//                       per-(pixel, row) arithmetic is eval_stats.h's stats_scan's, expression for expression, and every
+//                       accumulation is an integer one, so the two kernels write the same bits.
 //   group_rows_kernel   one work-item per row: eval_stats.h's finish_row with the row's own depth and camera row.
 #include "dcn_common.h"
 #include "eval_rows.h"
@@ -156,6 +163,130 @@ __global__ void __launch_bounds__(kMT) group_stats_kernel(GroupStats a) {
     }
 }
 
+constexpr int kWR = 256;          // rows (work-items) per workgroup of the wide kernel
+constexpr int kWT = 128;          // pixels per LDS tile (a quarter of it on the generic path, whose queries live in LDS too)
+
+struct WideStats {
+    GroupStats a;
+    int64_t strip;                 // pixels per workgroup
+};
+
+template <int DT>
+__global__ void __launch_bounds__(kWR) wide_stats_kernel(WideStats b) {
+    constexpr int TP = DT > 0 ? kWT : kWT / 4;          // (72 KiB of LDS on the generic path: two workgroups per CU)
+    constexpr int DM = DT > 0 ? DT : kMaxD;
+    __shared__ float s_pix[TP * DM];                       // the tile's descriptors, as they lie in memory: [pixel][D]
+    __shared__ unsigned char s_mask[TP];
+    __shared__ float s_q[DT > 0 ? 1 : kMaxD * kWR];        // generic path: the queries as [k][work-item]
+    const GroupStats& a = b.a;
+    const int D = DT > 0 ? DT : a.d;
+    const int g = blockIdx.z, w = a.w, tid = threadIdx.x;
+    const int64_t hw = a.hw;
+    const int64_t p0 = (int64_t)blockIdx.x * b.strip, p1 = p0 + b.strip < hw ? p0 + b.strip : hw;
+    const uint8_t* mask = a.mask_b + (size_t)g * hw;
+    if (blockIdx.y == 0) {   // num_pixels_in_masked_image (evaluation.py:1085), once per image: the first row block's strips
+        int n = 0;
+        for (int64_t p = p0 + tid; p < p1; p += kWR) n += mask[p] != 0 ? 1 : 0;
+        n = dcn::wave_sum<int>(n);
+        if ((tid & 63) == 0 && n) atomicAdd(a.mask_pixels + g, n);
+    }
+    int bad = 0;
+    int64_t lo;
+    int nq;
+    pair_rows(a.offsets, a.offsets_bad, g, a.max_rows, a.max_group_rows, lo, nq, bad);
+    if (bad && blockIdx.x == 0 && blockIdx.y == 0 && tid == 0) atomicOr(a.status, bad);
+    const int q0 = (int)blockIdx.y * kWR;
+    if (q0 >= nq) return;              // (uniform per workgroup)
+    const float* res = a.res_b + (size_t)g * hw * D;
+    const int64_t r = lo + q0 + tid;
+    const bool active = q0 + tid < nq && a.keep[r] != 0;   // a row left out and the work-items past the group's end idle
+    float q[DT > 0 ? DT : 1];
+    int gu = 0, gv = 0;
+    float tt = 0.f;
+    if (active) {
+        int rb = 0;
+        if (a.u_a[r] < 0 || a.u_a[r] >= w || a.v_a[r] < 0 || a.v_a[r] >= a.h) rb |= DCN_EVAL_BAD_INDEX;
+        gu = clip_round(a.u_b[r], w, rb);
+        gv = clip_round(a.v_b[r], a.h, rb);
+        if (rb && blockIdx.x == 0) atomicOr(a.status, rb);
+        const float* qs = a.queries + (size_t)r * D;
+        const float* gt = res + ((int64_t)gv * w + gu) * D;
+        float t2 = 0.f;                                    // stats_ground_truth's chain
+        if constexpr (DT > 0) {
+#pragma unroll
+            for (int k = 0; k < DT; ++k) {
+                q[k] = qs[k];
+                const float t = gt[k] - q[k];
+                t2 = fmaf(t, t, t2);
+            }
+        } else {
+            for (int k = 0; k < D; ++k) {
+                const float qk = qs[k];
+                s_q[k * kWR + tid] = qk;                   // (read back by this work-item only: no barrier)
+                const float t = gt[k] - qk;
+                t2 = fmaf(t, t, t2);
+            }
+        }
+        tt = sqrtf(t2);
+        if (blockIdx.x == 0) a.gt_d[r] = tt;               // once per row
+    }
+    unsigned long long k0 = ~0ull, k1 = ~0ull, s0 = 0ull, s1 = 0ull;
+    int n0 = 0, n1 = 0;
+    for (int64_t t0 = p0; t0 < p1; t0 += TP) {
+        const int tn = p1 - t0 < TP ? (int)(p1 - t0) : TP;
+        __syncthreads();
+        for (int i = tid; i < tn * D; i += kWR) s_pix[i] = res[t0 * D + i];
+        if (tid < tn) s_mask[tid] = mask[t0 + tid];
+        __syncthreads();
+        if (!active) continue;
+        int pu = (int)(t0 % w), pv = (int)(t0 / w);
+        for (int p = 0; p < tn; ++p) {                     // stats_scan's arithmetic for pixel t0 + p, this work-item's row
+            float d2 = 0.f;
+            if constexpr (DT > 0) {
+#pragma unroll
+                for (int k = 0; k < DT; ++k) {
+                    const float t = s_pix[p * DT + k] - q[k];
+                    d2 = fmaf(t, t, d2);
+                }
+            } else {
+                for (int k = 0; k < D; ++k) {
+                    const float t = s_pix[p * D + k] - s_q[k * kWR + tid];
+                    d2 = fmaf(t, t, d2);
+                }
+            }
+            const float dd = sqrtf(d2);
+            const float dm = s_mask[p] != 0 ? dd : dd + 1e6f;              // masked_norm_diffs
+            const unsigned pix = (unsigned)(t0 + p);
+            const unsigned long long c0k = (((unsigned long long)__float_as_uint(dd)) << 32) | pix;
+            const unsigned long long c1k = (((unsigned long long)__float_as_uint(dm)) << 32) | pix;
+            k0 = c0k < k0 ? c0k : k0;
+            k1 = c1k < k1 ? c1k : k1;
+            const bool c0 = dd < tt, c1 = dm < tt;
+            if (c0 || c1) {
+                const float du = (float)(pu - gu), dv = (float)(pv - gv);
+                const float pd = sqrtf(du * du + dv * dv);
+                const unsigned long long pf = (unsigned long long)((double)pd * dcn::kEvalSumScale + 0.5);
+                if (c0) { ++n0; s0 += pf; }
+                if (c1) { ++n1; s1 += pf; }
+            }
+            if (++pu == w) { pu = 0; ++pv; }
+        }
+    }
+    if (active) {                      // stats_scan's filter: almost every key loses against the word's value
+        const int64_t o0 = r, o1 = a.max_rows + r;
+        if (k0 != ~0ull && k0 < __atomic_load_n(a.best + o0, __ATOMIC_RELAXED)) atomicMin(a.best + o0, k0);
+        if (k1 != ~0ull && k1 < __atomic_load_n(a.best + o1, __ATOMIC_RELAXED)) atomicMin(a.best + o1, k1);
+        if (n0) {
+            atomicAdd(a.count + o0, n0);
+            atomicAdd(a.dist_sum + o0, s0);
+        }
+        if (n1) {
+            atomicAdd(a.count + o1, n1);
+            atomicAdd(a.dist_sum + o1, s1);
+        }
+    }
+}
+
 struct GroupRows {
     const uint16_t* depth_b;       // [G][hw]
     const uint16_t* depth_q;       // [rows] depth at the query pixel, millimetres
@@ -243,18 +374,22 @@ extern "C" size_t dcn_match_statistics_groups_workspace(int64_t max_rows) {
     return 2 * align256(r * 2 * sizeof(unsigned long long)) + align256(r * sizeof(float)) + 256;
 }
 
-extern "C" int dcn_match_statistics_groups(int g, int h, int w, int d, const float* res_b, const uint8_t* mask_b,
-                                           const uint16_t* depth_b, const float* queries, const int64_t* u_a, const int64_t* v_a,
-                                           const uint16_t* depth_q, const float* u_b, const float* v_b, const float* cams,
-                                           const uint8_t* keep, const int64_t* offsets, int64_t max_rows, int max_group_rows,
-                                           double* columns, uint8_t* is_valid, int32_t* pred_uv, int32_t* closer,
-                                           int32_t* row_pair, int32_t* mask_pixels, int32_t* status, void* workspace,
-                                           void* stream) {
+namespace {
+
+// The grouped statistics: the fills, the offsets check, the search (wide: wide_stats_kernel with strips of strip_pixels, 0 =
+// automatic; otherwise group_stats_kernel) and group_rows_kernel
+int run_groups(bool wide, int64_t strip_pixels, int g, int h, int w, int d, const float* res_b, const uint8_t* mask_b,
+               const uint16_t* depth_b, const float* queries, const int64_t* u_a, const int64_t* v_a, const uint16_t* depth_q,
+               const float* u_b, const float* v_b, const float* cams, const uint8_t* keep, const int64_t* offsets,
+               int64_t max_rows, int max_group_rows, double* columns, uint8_t* is_valid, int32_t* pred_uv, int32_t* closer,
+               int32_t* row_pair, int32_t* mask_pixels, int32_t* status, void* workspace, void* stream) {
     const int64_t hw = (int64_t)h * w;
     if (g < 1 || g > 65535 || h < 1 || w < 1 || hw >= ((int64_t)1 << 31) || d < 1 || d > kMaxD || !res_b || !mask_b || !depth_b ||
         !queries || !u_a || !v_a || !depth_q || !u_b || !v_b || !cams || !keep || !offsets || max_rows < 1 ||
         max_group_rows < 1 || !columns || !is_valid || !pred_uv || !closer || !row_pair || !mask_pixels || !status || !workspace)
         return DCN_E_INVALID;
+    const int row_blocks = dcn::ceil_div64(max_group_rows, kWR);
+    if (wide && (strip_pixels < 0 || row_blocks > 65535)) return DCN_E_INVALID;
     hipStream_t st = (hipStream_t)stream;
     char* ws = (char*)workspace;
     const size_t R = (size_t)max_rows;
@@ -291,17 +426,42 @@ extern "C" int dcn_match_statistics_groups(int g, int h, int w, int d, const flo
     a.h = h;
     a.d = d;
     a.max_group_rows = max_group_rows;
-    const dim3 grid((unsigned)dcn::ceil_div64(hw, kMT), (unsigned)g), block(kMT);
+    if (wide) {
+        WideStats ww;
+        ww.a = a;
+        if (strip_pixels > 0) {
+            ww.strip = strip_pixels < hw ? strip_pixels : hw;
+        } else {   // about four workgroups per CU of the 256: a keypoint-sized problem (8 images x 1 row block) gets 128 strips
+            const int64_t blocks = (int64_t)g * row_blocks;
+            const int64_t strips = blocks >= 1024 ? 1 : dcn::ceil_div64(1024, blocks);
+            int64_t sp = dcn::ceil_div64(hw, strips);
+            sp = sp < 4 * kWT ? 4 * kWT : sp;              // (at least four tiles between a row's atomics)
+            ww.strip = dcn::ceil_div64(sp, kWT) * kWT;
+        }
+        const dim3 grid((unsigned)dcn::ceil_div64(hw, ww.strip), (unsigned)row_blocks, (unsigned)g), block(kWR);
+#define DCN_WS(DT) hipLaunchKernelGGL((wide_stats_kernel<DT>), grid, block, 0, st, ww)
+        switch (d) {
+            case 3: DCN_WS(3); break;
+            case 4: DCN_WS(4); break;
+            case 8: DCN_WS(8); break;
+            case 16: DCN_WS(16); break;
+            case 32: DCN_WS(32); break;
+            default: DCN_WS(0); break;
+        }
+#undef DCN_WS
+    } else {
+        const dim3 grid((unsigned)dcn::ceil_div64(hw, kMT), (unsigned)g), block(kMT);
 #define DCN_GS(DT) hipLaunchKernelGGL((group_stats_kernel<DT>), grid, block, 0, st, a)
-    switch (d) {
-        case 3: DCN_GS(3); break;
-        case 4: DCN_GS(4); break;
-        case 8: DCN_GS(8); break;
-        case 16: DCN_GS(16); break;
-        case 32: DCN_GS(32); break;
-        default: DCN_GS(0); break;
-    }
+        switch (d) {
+            case 3: DCN_GS(3); break;
+            case 4: DCN_GS(4); break;
+            case 8: DCN_GS(8); break;
+            case 16: DCN_GS(16); break;
+            case 32: DCN_GS(32); break;
+            default: DCN_GS(0); break;
+        }
 #undef DCN_GS
+    }
     GroupRows b;
     b.depth_b = depth_b;
     b.depth_q = depth_q;
@@ -330,4 +490,30 @@ extern "C" int dcn_match_statistics_groups(int g, int h, int w, int d, const flo
     b.max_group_rows = max_group_rows;
     hipLaunchKernelGGL(group_rows_kernel, dim3((unsigned)dcn::ceil_div64(max_rows, 256)), dim3(256), 0, st, b);
     return dcn::check_launch();
+}
+
+}  // namespace
+
+extern "C" int dcn_match_statistics_groups(int g, int h, int w, int d, const float* res_b, const uint8_t* mask_b,
+                                           const uint16_t* depth_b, const float* queries, const int64_t* u_a, const int64_t* v_a,
+                                           const uint16_t* depth_q, const float* u_b, const float* v_b, const float* cams,
+                                           const uint8_t* keep, const int64_t* offsets, int64_t max_rows, int max_group_rows,
+                                           double* columns, uint8_t* is_valid, int32_t* pred_uv, int32_t* closer,
+                                           int32_t* row_pair, int32_t* mask_pixels, int32_t* status, void* workspace,
+                                           void* stream) {
+    return run_groups(false, 0, g, h, w, d, res_b, mask_b, depth_b, queries, u_a, v_a, depth_q, u_b, v_b, cams, keep, offsets,
+                      max_rows, max_group_rows, columns, is_valid, pred_uv, closer, row_pair, mask_pixels, status, workspace,
+                      stream);
+}
+
+extern "C" int dcn_match_statistics_groups_wide(int g, int h, int w, int d, const float* res_b, const uint8_t* mask_b,
+                                                const uint16_t* depth_b, const float* queries, const int64_t* u_a,
+                                                const int64_t* v_a, const uint16_t* depth_q, const float* u_b, const float* v_b,
+                                                const float* cams, const uint8_t* keep, const int64_t* offsets, int64_t max_rows,
+                                                int max_group_rows, int64_t strip_pixels, double* columns, uint8_t* is_valid,
+                                                int32_t* pred_uv, int32_t* closer, int32_t* row_pair, int32_t* mask_pixels,
+                                                int32_t* status, void* workspace, void* stream) {
+    return run_groups(true, strip_pixels, g, h, w, d, res_b, mask_b, depth_b, queries, u_a, v_a, depth_q, u_b, v_b, cams, keep,
+                      offsets, max_rows, max_group_rows, columns, is_valid, pred_uv, closer, row_pair, mask_pixels, status,
+                      workspace, stream);
 }

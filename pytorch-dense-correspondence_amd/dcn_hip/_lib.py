@@ -230,6 +230,8 @@ SYMBOLS = {
     "dcn_match_statistics_groups_workspace": (c_size_t, [c_int64]),
     "dcn_match_statistics_groups": (c_int, [c_int, c_int, c_int, c_int] + [c_void_p] * 12 + [c_int64, c_int]
                                     + [c_void_p] * 9),
+    "dcn_match_statistics_groups_wide": (c_int, [c_int, c_int, c_int, c_int] + [c_void_p] * 12 + [c_int64, c_int, c_int64]
+                                         + [c_void_p] * 9),
     "dcn_descriptor_statistics_workspace": (c_size_t, [c_int, c_int, c_int, c_int]),
     "dcn_descriptor_statistics": (c_int, [c_int, c_int, c_int, c_int] + [c_void_p] * 6),
     "dcn_descriptor_statistics_combine": (c_int, [c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p]),

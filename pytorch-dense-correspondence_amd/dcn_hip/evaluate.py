@@ -22,6 +22,14 @@ matches between DIFFERENT scenes.  ``cross_scene_labels`` resolves the annotated
 labelled pixels into them (``reproject_pixels``), runs the network once per distinct frame and computes the table's rows with
 every searched image read once (``match_statistics_groups``).
 
+``evaluate_network_cross_instance`` feeds the same chain with every combination of two pixel-labelled images.
+
+``evaluate_network_cross_scene_keypoints`` is the class-consistent keypoint table (evaluation.py:407-472, single_image_pair_
+cross_scene_keypoints_quantitative_analysis :1433-1552): named keypoints on different object instances, every combination of two
+labelled images, both orders (``keypoint_labels``, ``keypoint_rows``, ``evaluate_keypoint_rows``, ``keypoint_table``).  A labelled
+image is searched by (images - 1) * keypoints rows there, which is what ``match_statistics_groups_wide`` (the row-per-lane
+kernel of csrc/crossscene_kernels.hip) is for.
+
 ``evaluate_network_across_objects`` (csrc/acrossobj_kernels.hip) is its fourth part, ``evaluate_network_across_objects``
 (evaluation.py:305-337): pairs of frames of two different objects (``choose_object_pairs``), pixels sampled from mask a and
 their best matches over the whole of image b (``evaluate_object_pairs``: ``across_object_queries`` + ``best_match_pairs``).
@@ -677,7 +685,7 @@ def reproject_pixels(store, requests, K=None):
 
 
 def match_statistics_groups(res_b, mask_b, depth_b, queries, u_a, v_a, depth_q, u_b, v_b, cams, keep, offsets,
-                            max_group_rows=None):
+                            max_group_rows=None, _strip_pixels=None):
     """``match_statistics_pairs`` for GROUPS of rows that search one image, each row with a query of its own: every column of
     the reference's evaluation table, in two launches, with res_b read once whatever the number of rows.
 
@@ -728,12 +736,29 @@ def match_statistics_groups(res_b, mask_b, depth_b, queries, u_a, v_a, depth_q, 
     status = torch.empty(1, dtype=torch.int32, device=dev)
     ws = torch.empty(int(lib.dcn_match_statistics_groups_workspace(cap)), dtype=torch.uint8, device=dev)
     p = _lib.ptr
-    rc = lib.dcn_match_statistics_groups(G, h, w, d, p(rb), p(mb), p(db), p(q), p(ua), p(va), p(dq), p(ub), p(vb), p(cams),
-                                         p(kp), p(off), cap, mgr, p(cols), p(valid), p(pred), p(closer), p(row_pair),
-                                         p(mask_pixels), p(status), p(ws), _lib.stream_ptr())
-    _lib.check(rc, "dcn_match_statistics_groups")
+    rows_in = (G, h, w, d, p(rb), p(mb), p(db), p(q), p(ua), p(va), p(dq), p(ub), p(vb), p(cams), p(kp), p(off), cap, mgr)
+    rows_out = (p(cols), p(valid), p(pred), p(closer), p(row_pair), p(mask_pixels), p(status), p(ws), _lib.stream_ptr())
+    if _strip_pixels is None:
+        _lib.check(lib.dcn_match_statistics_groups(*(rows_in + rows_out)), "dcn_match_statistics_groups")
+    else:                                                   # (match_statistics_groups_wide)
+        _lib.check(lib.dcn_match_statistics_groups_wide(*(rows_in + (int(_strip_pixels),) + rows_out)),
+                   "dcn_match_statistics_groups_wide")
     return EvalTable(cols[:, :R], valid[:, :R], pred[:, :R], closer[:, :R], row_pair[:R], off, mask_pixels, status,
                      u_a, v_a, u_b, v_b)
+
+
+def match_statistics_groups_wide(res_b, mask_b, depth_b, queries, u_a, v_a, depth_q, u_b, v_b, cams, keep, offsets,
+                                 max_group_rows=None, strip_pixels=0):
+    """``match_statistics_groups`` -- its arguments, its EvalTable, its bits -- by the row-per-lane kernel
+    (``dcn_match_statistics_groups_wide``), made for groups of MANY rows: a workgroup takes up to 256 rows of one group and a
+    strip of ``strip_pixels`` pixels of its image (0: chosen by the library so that the grid fills the device) and every
+    work-item keeps one row's running keys, counts and sums while the strip's pixels pass by, with no reduction across
+    lanes.  Every accumulation is an integer one (packed-key minima, counts, distance sums in units of 2^-20 pixel), so the
+    result does not depend on ``strip_pixels`` and equals match_statistics_groups' bit for bit.  No host synchronization."""
+    if int(strip_pixels) < 0:
+        raise ValueError("strip_pixels must be >= 0 (0 = automatic), got %d" % int(strip_pixels))
+    return match_statistics_groups(res_b, mask_b, depth_b, queries, u_a, v_a, depth_q, u_b, v_b, cams, keep, offsets,
+                                   max_group_rows, _strip_pixels=int(strip_pixels))
 
 
 def _gather_frame_list(store, frames, want):
@@ -756,6 +781,62 @@ def _cross_scene_views(labels, views):
                        or v[:, 1].max() >= labels.pixels.shape[0] or v[:, 2].min() < LABELLED or v[:, 2].max() > VIEW_OF_B):
         raise ValueError("views name a pair, a label or a kind outside the labels")
     return v
+
+
+def _search_rows_by_frame(dcn, store, out, word, fb, kept, pair, queries, depth_q, cams, keep, batch_frames, max_search_bytes,
+                          mean, std, statistics, resident=None):
+    """The search of evaluate_cross_scene_rows and evaluate_keypoint_rows: the rows ``kept`` (host indices into the T rows of
+    the nan-filled EvalTable ``out``, whose u_a .. v_b are the rows' pixels) sorted by the frame ``fb`` they search, one group
+    per frame; the searched frames in chunks whose descriptor images stay within ``max_search_bytes`` -- forwarded through
+    ``dcn``, or taken from ``resident`` = (sorted frames, their descriptor images) -- and one ``statistics`` call
+    (match_statistics_groups or its wide twin) per chunk, whose rows go back to their places in ``out``; ``row_pair`` becomes
+    ``pair`` of the row and ``mask_pixels`` the mask pixels of the image it searched.  -> the status word, joined to ``word``"""
+    dev, h, w, d = store.device, store.h, store.w, int(queries.shape[1])
+    up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+    b_frames, b_group = np.unique(fb[kept], return_inverse=True)
+    by_group = np.argsort(b_group, kind="stable")
+    order = up(kept[by_group])                                # table rows in search order
+    g_off = np.searchsorted(b_group[by_group], np.arange(len(b_frames) + 1)).astype(np.int64)
+    g_off_dev = up(g_off)
+    per_chunk = min(1024, max(1, int(max_search_bytes) // (h * w * d * 4)))      # (images per statistics call)
+    mask_pixels = out.mask_pixels
+    for g0 in range(0, len(b_frames), per_chunk):
+        g1 = min(g0 + per_chunk, len(b_frames))
+        if resident is None:
+            rgb, depth_b, mask_b, bad = _gather_frame_list(store, b_frames[g0:g1], ("rgb", "depth", "mask"))
+            res = []
+            _forward_in_eval_mode(dcn, rgb, mask_b, None, None, int(batch_frames), mean, std, lambda lo, n, y: res.append(y))
+            res_b = (res[0] if len(res) == 1 else torch.cat(res)).float().contiguous()
+            del rgb, res
+        else:
+            _, depth_b, mask_b, bad = _gather_frame_list(store, b_frames[g0:g1], ("depth", "mask"))
+            at = np.searchsorted(resident[0], b_frames[g0:g1])
+            res_b = resident[1][int(at[0]):int(at[-1]) + 1] if int(at[-1]) - int(at[0]) + 1 == len(at) else resident[1][up(at)]
+        word = word | (bad & 1) * BAD_FRAME
+        rows = order[g_off[g0]:g_off[g1]]
+        t = statistics(res_b, mask_b, depth_b, queries[rows], out.u_a[rows], out.v_a[rows], depth_q[rows], out.u_b[rows],
+                       out.v_b[rows], cams[rows], keep[rows], g_off_dev[g0:g1 + 1] - int(g_off[g0]),
+                       max_group_rows=int(np.diff(g_off[g0:g1 + 1]).max()))
+        del res_b
+        out.columns[:, rows], out.is_valid[:, rows], out.pred_uv[:, rows], out.closer[:, rows] = (t.columns, t.is_valid,
+                                                                                                   t.pred_uv, t.closer)
+        has = t.row_pair >= 0
+        out.row_pair[rows] = torch.where(has, up(pair[kept[by_group][g_off[g0]:g_off[g1]]].astype(np.int32)), t.row_pair)
+        mask_pixels[rows] = torch.where(has, t.mask_pixels[t.row_pair.clamp_min(0).long()], torch.zeros_like(t.row_pair))
+        word = word | t.status
+    return word
+
+
+def _camera_rows_of(store, fr, host_keep):
+    """Camera rows (K of slot 0's scene, K^-1, pose of slot 0, inverse pose of slot 1) for T rows from ``dcn_gather_frames``
+    over ``fr`` (host int [T, 2]); rows without both frames (``host_keep`` false) reach the gather as frame 0 -- they are
+    left out anyway.  -> (cams float32 [T, 50], BAD_FRAME status word)"""
+    cams, word = [], 0
+    for lo in range(0, int(fr.shape[0]), 16384):
+        got = _gather_host_frames(store, np.where(host_keep[lo:lo + 16384, None], fr[lo:lo + 16384], 0), ("cams",))
+        cams.append(got[3][0])
+        word = word | (got[4] & 1) * BAD_FRAME
+    return torch.cat(cams), word
 
 
 def evaluate_cross_scene_rows(dcn, store, labels, views, *, batch_frames=16, max_search_bytes=2 << 30,
@@ -833,42 +914,12 @@ def evaluate_cross_scene_rows(dcn, store, labels, views, *, batch_frames=16, max
     d = int(queries.shape[1])
     depth_q = store.depth[up(np.where(host_keep, fa, 0)), v_a, u_a]
     # camera rows per row (frames of rows without both reach the gather as frame 0: the row is left out anyway)
-    cams = []
-    for lo in range(0, T, 16384):
-        fr = np.where(host_keep[lo:lo + 16384, None], v[lo:lo + 16384, 3:5], 0)
-        got = _gather_host_frames(store, fr, ("cams",))
-        cams.append(got[3][0])
-        word = word | (got[4] & 1) * BAD_FRAME
-    cams = torch.cat(cams)
-    # 3. the rows by the frame they search, the searched frames in chunks
-    b_frames, b_group = np.unique(fb[kept], return_inverse=True)
-    by_group = np.argsort(b_group, kind="stable")
-    order = up(kept[by_group])                                # table rows in search order
-    g_off = np.searchsorted(b_group[by_group], np.arange(len(b_frames) + 1)).astype(np.int64)
-    g_off_dev = up(g_off)
-    per_chunk = min(1024, max(1, int(max_search_bytes) // (h * w * d * 4)))      # (images per match_statistics_groups call)
+    cams, bad = _camera_rows_of(store, v[:, 3:5], host_keep)
+    word = word | bad
+    # 3. the rows by the frame they search, the searched frames in chunks; 4. back into the order of ``views``
     out = nan_table()
-    mask_pixels = out.mask_pixels
-    for g0 in range(0, len(b_frames), per_chunk):
-        g1 = min(g0 + per_chunk, len(b_frames))
-        rgb, depth_b, mask_b, bad = _gather_frame_list(store, b_frames[g0:g1], ("rgb", "depth", "mask"))
-        word = word | (bad & 1) * BAD_FRAME
-        res = []
-        _forward_in_eval_mode(dcn, rgb, mask_b, None, None, int(batch_frames), mean, std, lambda lo, n, y: res.append(y))
-        res_b = (res[0] if len(res) == 1 else torch.cat(res)).float().contiguous()
-        del rgb, res
-        rows = order[g_off[g0]:g_off[g1]]
-        t = match_statistics_groups(res_b, mask_b, depth_b, queries[rows], u_a[rows], v_a[rows], depth_q[rows], u_b[rows],
-                                    v_b[rows], cams[rows], keep[rows], g_off_dev[g0:g1 + 1] - int(g_off[g0]),
-                                    max_group_rows=int(np.diff(g_off[g0:g1 + 1]).max()))
-        del res_b
-        # 4. back into the order of ``views``
-        out.columns[:, rows], out.is_valid[:, rows], out.pred_uv[:, rows], out.closer[:, rows] = (t.columns, t.is_valid,
-                                                                                                   t.pred_uv, t.closer)
-        has = t.row_pair >= 0
-        out.row_pair[rows] = torch.where(has, up(pair[kept[by_group][g_off[g0]:g_off[g1]]].astype(np.int32)), t.row_pair)
-        mask_pixels[rows] = torch.where(has, t.mask_pixels[t.row_pair.clamp_min(0).long()], torch.zeros_like(t.row_pair))
-        word = word | t.status
+    word = _search_rows_by_frame(dcn, store, out, word, fb, kept, pair, queries, depth_q, cams, keep, int(batch_frames),
+                                 int(max_search_bytes), mean, std, match_statistics_groups)
     return out._replace(status=word.to(torch.int32))
 
 
@@ -921,6 +972,260 @@ def evaluate_network_cross_scene(dcn, store, annotated_pairs, num_views_a=10, nu
         df = pandas.DataFrame({k: table[k] for k in names})
     except ImportError:
         df = None
+    return table, df
+
+
+def evaluate_network_cross_instance(dcn, store, labelled_images, num_views_a=10, num_views_b=10, host_rng=None):
+    """``DenseCorrespondenceEvaluation.evaluate_network_cross_instance`` (evaluation.py:350-404) on a frame store:
+    ``labelled_images`` is the reference's list of dicts {"image": {scene_name, image_idx, pixels: [{u, v}, ...]}} (or a path to
+    its YAML); every ``itertools.combinations(labelled_images, 2)`` becomes an annotated pair (image_a, image_b) in that order
+    and the list goes to ``evaluate_network_cross_scene``.  -> (table, dataframe) as it returns them."""
+    import itertools
+    if isinstance(labelled_images, str):
+        labelled_images = _yaml_file(labelled_images)
+    pairs = [{"image_a": a["image"], "image_b": b["image"]} for a, b in itertools.combinations(labelled_images, 2)]
+    return evaluate_network_cross_scene(dcn, store, pairs, num_views_a, num_views_b, host_rng)
+
+
+# ---- class-consistent keypoints (evaluation.py:407-472, :1433-1552, :2413-2462) ----------------------------------------------
+KeypointLabels = collections.namedtuple("KeypointLabels", "images names uv object_ids size skipped")
+KEYPOINT_ROW_COLUMNS = ("combination", "keypoint", "order", "frame_1", "frame_2", "u_1", "v_1", "u_2", "v_2", "k_frame")
+KEYPOINT_COLUMNS = ("img_a_idx", "img_b_idx", "scene_name_a", "scene_name_b", "object_id_a", "object_id_b", "keypoint_name")
+STANDARD, REVERSE = 0, 1                      # a row's order in keypoint_rows' table
+WIDE_GROUP_MIN_ROWS = 24                      # evaluate_keypoint_rows(search=None): mean rows per searched image from which
+#                                               the wide entry is used.  Measured (profiles/keypoint_bench_crossover.json, 8
+#                                               images of 640x480): at 21 rows the two entries tie (1.29x at D = 3, 0.96x at
+#                                               D = 16), at 28 the wide one wins at both (1.66x, 1.25x), at 14 it loses
+
+
+def _yaml_file(path):
+    import yaml
+    with open(path) as f:
+        return yaml.safe_load(f)
+
+
+def keypoint_labels(store, annotations):
+    """The reference's class-consistent keypoint annotations (evaluation/utils.py:59-81: a list of dicts {scene_name,
+    image_idx, object_id, keypoints: {name: {u, v, ...}}}, or a path to its YAML) resolved to the frames of ``store`` through
+    ``store.scene_names`` / ``store.frame_ids``, as ``cross_scene_labels`` resolves its pairs.
+
+    -> KeypointLabels: ``images`` int64 [K, 3] of (index in ``annotations``, scene, frame), frame as a store index; ``names``:
+    per image the keypoint names in the order of its mapping; ``uv``: per image float64 [M, 2], u and v AS GIVEN (they are
+    rounded per row, keypoint_rows); ``object_ids``: per image, the annotation's; ``size`` (h, w) of the store's images;
+    ``skipped``: [(index, reason)] for the images whose scene or image the store does not hold.  ValueError for an empty
+    list."""
+    if isinstance(annotations, str):
+        annotations = _yaml_file(annotations)
+    if annotations is None or len(annotations) == 0:
+        raise ValueError("no keypoint annotations given")
+    first = store.scene_first_frame_host
+    images, names, uv, object_ids, skipped = [], [], [], [], []
+    for i, an in enumerate(annotations):
+        if an["scene_name"] not in store.scene_names:
+            skipped.append((i, "the store holds no scene %r" % (an["scene_name"],)))
+            continue
+        sc = store.scene_names.index(an["scene_name"])
+        ids = [int(x) for x in store.frame_ids[sc]]
+        if int(an["image_idx"]) not in ids:
+            skipped.append((i, "scene %r holds no image %r" % (an["scene_name"], an["image_idx"])))
+            continue
+        images.append([i, sc, first[sc] + ids.index(int(an["image_idx"]))])
+        names.append([str(k) for k in an["keypoints"]])
+        uv.append(np.asarray([[float(kp["u"]), float(kp["v"])] for kp in an["keypoints"].values()], np.float64).reshape(-1, 2))
+        object_ids.append(an.get("object_id"))
+    return KeypointLabels(np.asarray(images, np.int64).reshape(-1, 3), names, uv, object_ids, (int(store.h), int(store.w)),
+                          skipped)
+
+
+def keypoint_rows(labels, reference_query_pixel=True):
+    """The rows of single_image_pair_cross_scene_keypoints_quantitative_analysis (evaluation.py:1433-1552) over
+    ``itertools.combinations(images, 2)`` (:447), on the host and in the reference's order: per combination the keypoints of
+    its FIRST image in that image's order, per keypoint "standard" (image 1 = the first image, searched image 2 = the second)
+    then "reverse".
+
+    Kept from the reference ON PURPOSE: ValueError("keypoint %s appears in one list of annotated data but not the other") when
+    a name of the first image is missing from the second, while extra names of the second are ignored (:1505-1508); the query
+    pixel is (u of image 1, v of image 2) -- evaluation.py:1523 as written, ``(data[idx_1]['u'], data[idx_2]['v'])`` --
+    unless ``reference_query_pixel`` is False, which gives (u_1, v_1); both pixels go through
+    clip_pixel_to_image_size_and_round (Python 2's ``round``, ``min(..., size - 1)``), and a pixel that rounds below zero is
+    a ValueError as in ``cross_scene_labels``; the K of a row is that of the scene of the combination's FIRST image for both
+    orders (:1490-1495).
+
+    -> int64 array [R, 10] in the order of KEYPOINT_ROW_COLUMNS: combination (its index in ``itertools.combinations``),
+    keypoint (index among the first image's names), order (STANDARD / REVERSE), frame 1 (the query's), frame 2 (the searched
+    one), u_1, v_1 (the query pixel), u_2, v_2 (the ground truth in frame 2), and the frame whose scene supplies K; frames as
+    store indices."""
+    import itertools
+    h, w = labels.size
+    out = []
+    for c, (i, j) in enumerate(itertools.combinations(range(labels.images.shape[0]), 2)):
+        for k, name in enumerate(labels.names[i]):
+            if name not in labels.names[j]:
+                raise ValueError("keypoint %s appears in one list of annotated data but not the other" % (name,))
+            data = (labels.uv[i][k], labels.uv[j][labels.names[j].index(name)])
+            for order, (i1, i2) in ((STANDARD, (0, 1)), (REVERSE, (1, 0))):
+                query = (data[i1][0], data[i2][1] if reference_query_pixel else data[i1][1])
+                px = [min(_py2_round(x), size - 1) for x, size in ((query[0], w), (query[1], h), (data[i2][0], w),
+                                                                   (data[i2][1], h))]
+                if min(px) < 0:
+                    raise ValueError("keypoint %s of annotations %d / %d: a labelled pixel is negative" % (
+                        name, labels.images[i, 0], labels.images[j, 0]))
+                frames = (labels.images[i, 2], labels.images[j, 2])
+                out.append([c, k, order, frames[i1], frames[i2]] + px + [frames[0]])
+    return np.asarray(out, np.int64).reshape(-1, len(KEYPOINT_ROW_COLUMNS))
+
+
+def _keypoint_rows_table(store, rows):
+    r = np.asarray(rows.cpu() if torch.is_tensor(rows) else rows)
+    if r.ndim != 2 or r.shape[1] != len(KEYPOINT_ROW_COLUMNS) or not np.issubdtype(r.dtype, np.integer):
+        raise ValueError("rows must be keypoint_rows' integer table [R, %d], got %s" % (len(KEYPOINT_ROW_COLUMNS), r.shape))
+    r = r.astype(np.int64)
+    if r.shape[0] and (r[:, [3, 4, 9]].min() < 0 or r[:, [3, 4, 9]].max() >= store.num_frames):
+        raise ValueError("rows name a frame outside the store's %d frames" % store.num_frames)
+    return r
+
+
+def evaluate_keypoint_rows(dcn, store, labels, rows, *, batch_frames=16, max_search_bytes=2 << 30, search=None,
+                           mean=_aug.DEFAULT_IMAGE_MEAN, std=_aug.DEFAULT_IMAGE_STD_DEV):
+    """compute_descriptor_match_statistics for every row of ``rows`` (keypoint_rows' table over ``labels``) on the device,
+    nothing read back: 1. ``dcn.forward_image_tensors`` in eval mode ONCE per distinct labelled frame (the reference caches
+    per (scene, image_idx) too, :428-441), ``batch_frames`` at a time, keeping the rows' query descriptors -- and the
+    descriptor images themselves when all of them fit in ``max_search_bytes``; otherwise evaluate_cross_scene_rows' two
+    sweeps: the searched frames are forwarded again, chunk by chunk; 2. the rows sorted by the frame they search, one group per
+    frame, camera rows from ``dcn_gather_frames`` over (frame 1, frame 2) with the K and K^-1 slots replaced by those of the
+    row's K frame; 3. the statistics by ``search``: "wide" (match_statistics_groups_wide), "groups" (match_statistics_groups)
+    or None: wide from WIDE_GROUP_MIN_ROWS rows per searched image on average.  Both give the same bits, so the choice does
+    not show in the result.
+
+    -> EvalTable with one row per row of ``rows``, in that order: ``row_pair`` the row's combination; ``offsets`` int64 [C + 1],
+    the combinations' row ranges; ``mask_pixels`` int32 [R], PER ROW: the mask pixels of the image the row searched; u_a, v_a
+    the query pixel, u_b, v_b the ground truth; ``status``: the statistics' bits and BAD_FRAME for the gathers.
+    ``dcn.training`` is left as found."""
+    v = _keypoint_rows_table(store, rows)
+    if int(batch_frames) < 1 or int(max_search_bytes) < 1:
+        raise ValueError("batch_frames and max_search_bytes must be >= 1")
+    if search not in (None, "wide", "groups"):
+        raise ValueError('search must be None, "wide" or "groups", got %r' % (search,))
+    T, dev, h, w = int(v.shape[0]), store.device, store.h, store.w
+    if T == 0:
+        raise ValueError("no keypoint rows given")
+    up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+    comb, fa, fb, kf = v[:, 0], v[:, 3], v[:, 4], v[:, 9]
+    u_a, v_a = up(v[:, 5]), up(v[:, 6])
+    u_b, v_b = up(v[:, 7].astype(np.float32)), up(v[:, 8].astype(np.float32))
+    keep = torch.ones(T, dtype=torch.uint8, device=dev)
+    word = torch.zeros(1, dtype=torch.int32, device=dev)
+    ncomb = int(comb.max()) + 1
+    offsets = up(np.searchsorted(comb, np.arange(ncomb + 1)).astype(np.int64))
+    # 1. one forward pass per distinct labelled frame
+    frames = np.unique(np.concatenate([fa, fb]))
+    slot = np.searchsorted(frames, fa)
+    by_slot = np.argsort(slot, kind="stable")
+    a_rows, a_local = up(by_slot), up(slot[by_slot])
+    a_bounds = np.searchsorted(slot[by_slot], np.arange(len(frames) + 1))
+    rgb, _, mask, bad = _gather_frame_list(store, frames, ("rgb", "mask"))
+    word = word | (bad & 1) * BAD_FRAME
+    queries, images = [], []
+
+    def take(lo, n, res):
+        if not queries:
+            queries.append(torch.zeros((T, int(res.shape[3])), dtype=torch.float32, device=dev))
+            if len(frames) * h * w * int(res.shape[3]) * 4 <= int(max_search_bytes):      # every image stays
+                images.append(torch.empty((len(frames), h, w, int(res.shape[3])), dtype=torch.float32, device=dev))
+        at = a_rows[a_bounds[lo]:a_bounds[lo + n]]
+        queries[0][at] = res[a_local[a_bounds[lo]:a_bounds[lo + n]] - lo, v_a[at], u_a[at]].float()
+        if images:
+            images[0][lo:lo + n] = res
+    _forward_in_eval_mode(dcn, rgb, mask, None, None, int(batch_frames), mean, std, take)
+    del rgb, mask
+    queries = queries[0]
+    depth_q = store.depth[up(fa), v_a, u_a]
+    # 2. camera rows: pose 1 and pose 2^-1 of the row's frames, K and K^-1 of the combination's first image
+    cams, bad = _camera_rows_of(store, v[:, 3:5], np.ones(T, bool))
+    of_k, bad_k = _camera_rows_of(store, np.stack([kf, kf], axis=1), np.ones(T, bool))
+    cams[:, :18] = of_k[:, :18]
+    word = word | bad | bad_k
+    # 3. the rows by the frame they search
+    if search is None:
+        search = "wide" if T >= WIDE_GROUP_MIN_ROWS * len(np.unique(fb)) else "groups"
+    out = EvalTable(
+        torch.full((len(COLUMNS), T), float("nan"), dtype=torch.float64, device=dev),
+        torch.zeros((2, T), dtype=torch.uint8, device=dev), torch.full((4, T), -1, dtype=torch.int32, device=dev),
+        torch.zeros((2, T), dtype=torch.int32, device=dev), torch.full((T,), -1, dtype=torch.int32, device=dev), offsets,
+        torch.zeros(T, dtype=torch.int32, device=dev), word, u_a, v_a, u_b, v_b)
+    word = _search_rows_by_frame(dcn, store, out, word, fb, np.arange(T), comb, queries, depth_q, cams, keep, int(batch_frames),
+                                 int(max_search_bytes), mean, std,
+                                 match_statistics_groups_wide if search == "wide" else match_statistics_groups,
+                                 resident=(frames, images[0]) if images else None)
+    return out._replace(status=word.to(torch.int32))
+
+
+def keypoint_table(store, labels, rows, t):
+    """evaluate_keypoint_rows' EvalTable ``t`` (over ``rows``) as the reference's table, with ONE copy to the host: a dict of
+    numpy columns under the reference's column names (COLUMNS as float64, ``is_valid`` / ``is_valid_masked`` as bool) plus
+    KEYPOINT_COLUMNS by the row's order (evaluation.py:1541-1547): ``img_a_idx`` / ``scene_name_a`` / ``object_id_a`` of the
+    image the query comes from, ``..._b`` of the image searched, and ``keypoint_name``.  RuntimeError when the chain's status
+    word is not zero."""
+    import itertools
+    rows = _keypoint_rows_table(store, rows)
+    # one transfer: everything packed into one float64 block (ints up to 2^31 are exact)
+    block = torch.cat([t.columns, t.is_valid.double(), t.status.double().expand_as(t.row_pair).view(1, -1)]).cpu().numpy()
+    if block.shape[1] and int(block[-1, 0]):
+        raise RuntimeError("dcn_hip: the keypoint evaluation failed on the device (status %d)" % int(block[-1, 0]))
+    table = {k: block[i].copy() for i, k in enumerate(COLUMNS)}
+    table["is_valid"] = block[len(COLUMNS)] != 0
+    table["is_valid_masked"] = block[len(COLUMNS) + 1] != 0
+    combos = np.asarray(list(itertools.combinations(range(labels.images.shape[0]), 2)), np.int64).reshape(-1, 2)
+    first = np.asarray(store.scene_first_frame_host, np.int64)
+    pair = combos[rows[:, 0]]                                                   # (first image, second image) per row
+    table["keypoint_name"] = np.array([labels.names[i][k] for i, k in zip(pair[:, 0], rows[:, 1])], dtype=object)
+    reverse = rows[:, 2] == REVERSE
+    for side, image in (("a", np.where(reverse, pair[:, 1], pair[:, 0])), ("b", np.where(reverse, pair[:, 0], pair[:, 1]))):
+        scene, frame = labels.images[image, 1], labels.images[image, 2]
+        table["scene_name_" + side] = np.array([store.scene_names[s] for s in scene], dtype=object)
+        table["img_%s_idx" % side] = np.array([int(store.frame_ids[s][f - first[s]]) for s, f in zip(scene, frame)],
+                                              dtype=np.int64)
+        table["object_id_" + side] = np.array([labels.object_ids[i] for i in image], dtype=object)
+    return table
+
+
+def evaluate_network_cross_scene_keypoints(dcn, store, annotations, save_to=None):
+    """``DenseCorrespondenceEvaluation.evaluate_network_cross_scene_keypoints`` (evaluation.py:407-472) on a frame store:
+    keypoint_labels, keypoint_rows, evaluate_keypoint_rows, then keypoint_table's ONE copy to the host.  -> (table,
+    dataframe) like ``evaluate_network``: ``table`` as keypoint_table returns it; ``dataframe`` a ``pandas.DataFrame`` of it
+    when pandas imports, else None.  ``save_to``: a folder that receives ``data.csv``, the file
+    run_cross_instance_keypoint_evaluation_on_network (:2413-2462) writes into ``<model folder>/analysis/
+    cross_scene_keypoints`` (by pandas when it imports, otherwise by the csv module with the same header and index column).
+    Fewer than two usable labelled images give an empty table.  ``dcn.training`` is left as found."""
+    labels = keypoint_labels(store, annotations)
+    rows = keypoint_rows(labels)
+    names = COLUMNS + ("is_valid", "is_valid_masked") + KEYPOINT_COLUMNS
+    if rows.shape[0] == 0:
+        table = {k: np.zeros(0, np.float64) for k in COLUMNS}
+        table.update(is_valid=np.zeros(0, bool), is_valid_masked=np.zeros(0, bool), img_a_idx=np.zeros(0, np.int64),
+                     img_b_idx=np.zeros(0, np.int64))
+        table.update({k: np.zeros(0, object) for k in KEYPOINT_COLUMNS if k not in table})
+    else:
+        table = keypoint_table(store, labels, rows, evaluate_keypoint_rows(dcn, store, labels, rows))
+    assert set(table) == set(names)
+    try:
+        import pandas
+        df = pandas.DataFrame({k: table[k] for k in names})
+    except ImportError:
+        df = None
+    if save_to is not None:
+        if not os.path.isdir(save_to):
+            os.makedirs(save_to)
+        path = os.path.join(save_to, "data.csv")
+        if df is not None:
+            df.to_csv(path)
+        else:
+            import csv
+            with open(path, "w", newline="") as f:
+                out = csv.writer(f)
+                out.writerow(("",) + names)
+                for i in range(len(table["is_valid"])):
+                    out.writerow([i] + [table[k][i] for k in names])
     return table, df
 
 
