@@ -1106,6 +1106,56 @@ int dcn_descriptor_statistics(int n, int h, int w, int d, const float* res, cons
 int dcn_descriptor_statistics_combine(int n, int d, const float* per_image, const int32_t* mask_pixels, int num_images,
                                       float* stats, int32_t* used, void* stream);
 
+/* =====================================================================================================
+ * 13. Training from a frame store with no host read -- the bookkeeping of DenseCorrespondenceTraining.run()
+ *     (dense_correspondence/training/training.py:290-456) around the step, decided on the device: whether the iteration
+ *     counts (the `continue` on an empty sample, :304-306), the learning-rate schedule (adjust_learning_rate, :544-558, which
+ *     runs AFTER that `continue`), the optimizer step, the batch-norm buffers of a skipped iteration, and the log
+ *     (update_plots, :353-413).  All entries are asynchronous on `stream` and read nothing back.
+ *
+ * 13a. dcn_train_advance: one launch of one work-item, BEFORE the forward pass.  types int32 [B] (SampleBatch.type: -1 for
+ *     an empty pair).  active = any(types[p] != -1); if active: when iteration % steps_between_decay == 0, lr *= decay (a
+ *     double multiply: the bits of Python's); t += 1; step_size = (float)(lr / (1 - beta1^t)); bc2_sqrt =
+ *     (float)sqrt(1 - beta2^t) -- the operations of dcn_adam_step's host code in the same order (double, beta^t by repeated
+ *     squaring, rounded once), bit for bit its floats; num_active += 1.  If not: num_skipped += 1, nothing else changes.
+ *     B >= 1, steps_between_decay >= 1, decay >= 0, betas in [0, 1).
+ * 13b. dcn_adam_step_guarded: dcn_adam_step's launches (tables of 80 tensors, 4096 elements per workgroup, 16-byte path
+ *     when the four pointers allow it) with step_size and bc2_sqrt read from the state; a workgroup that finds
+ *     state->active == 0 returns before it touches a tensor.  28 bytes per element plus one uniform load per workgroup.
+ * 13c. dcn_guarded_copy: n buffers dst[i] <- src[i] of bytes[i] bytes (dst, src, bytes: HOST arrays; 4-byte aligned pointers,
+ *     bytes[i] % 4 == 0, bytes[i] < 2^31), performed when state->active == when_active; state == NULL copies
+ *     unconditionally.  One workgroup per buffer, tables of 128 buffers per launch.
+ * 13d. dcn_train_log: row `row` of history (float64 [rows][DCN_TRAIN_LOG_COLUMNS]):
+ *       0 iteration, 1 active, 2 lr, 3 num_valid (pairs of a type in 0 .. 4), 4 loss (the float at `loss`),
+ *       5 + 2k, 6 + 2k for term k of terms float [B][5] (loss, match, masked, background, blind): the mean of terms[p][k]
+ *       over the pairs p whose TYPE composes term k, added in pair order in double, and the number of those pairs (mean 0
+ *       where there is none).  Types 0, 3 and 4 (within scene, multi object, synthetic multi object) compose every term;
+ *       types 1 and 2 (across scene, different object) the loss and the blind term (loss_composer.py:26-64, :168-212: the
+ *       others are zero_loss()); type -1 none.
+ *       15 the type of the first pair that is not empty (-1 when all are).
+ *     One launch of one workgroup.  B >= 1, row >= 0 (the caller keeps it below the rows allocated).
+ * ===================================================================================================== */
+struct dcn_train_state {
+    int32_t active;         /* this iteration counts (set by dcn_train_advance) */
+    int32_t reserved;
+    int64_t t;              /* Adam step count: the active iterations so far */
+    double lr;
+    float step_size;        /* lr / (1 - beta1^t) */
+    float bc2_sqrt;         /* sqrt(1 - beta2^t) */
+    int64_t num_active;
+    int64_t num_skipped;
+};
+#define DCN_TRAIN_LOG_COLUMNS 16
+int dcn_train_advance(struct dcn_train_state* state, const int32_t* types, int B, int64_t iteration,
+                      int64_t steps_between_decay, double decay, double beta1, double beta2, void* stream);
+int dcn_adam_step_guarded(int n, void* const* param, const void* const* grad, void* const* exp_avg, void* const* exp_avg_sq,
+                          const int64_t* numel, double eps, double weight_decay, double beta1, double beta2,
+                          const struct dcn_train_state* state, void* stream);
+int dcn_guarded_copy(int n, void* const* dst, const void* const* src, const int64_t* bytes,
+                     const struct dcn_train_state* state, int when_active, void* stream);
+int dcn_train_log(double* history, int64_t row, int64_t iteration, const struct dcn_train_state* state, const float* loss,
+                  const float* terms, const int32_t* types, int B, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

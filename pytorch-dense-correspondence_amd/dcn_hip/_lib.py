@@ -235,6 +235,12 @@ SYMBOLS = {
     "dcn_descriptor_statistics_workspace": (c_size_t, [c_int, c_int, c_int, c_int]),
     "dcn_descriptor_statistics": (c_int, [c_int, c_int, c_int, c_int] + [c_void_p] * 6),
     "dcn_descriptor_statistics_combine": (c_int, [c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p]),
+    "dcn_train_advance": (c_int, [c_void_p, c_void_p, c_int, c_int64, c_int64, ctypes.c_double, ctypes.c_double,
+                                  ctypes.c_double, c_void_p]),
+    "dcn_adam_step_guarded": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, ctypes.c_double,
+                                      ctypes.c_double, ctypes.c_double, ctypes.c_double, c_void_p, c_void_p]),
+    "dcn_guarded_copy": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
+    "dcn_train_log": (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
 }
 
 ERRORS = {-1: "DCN_E_INVALID (bad argument)", -2: "DCN_E_LAUNCH (kernel launch failed)",

@@ -1,0 +1,348 @@
+"""Training from a frame store with no host read: the reference's ``DenseCorrespondenceTraining.run()``
+(dense_correspondence/training/training.py:228-456) over a ``dcn_hip.frames.FrameStore``.
+
+The reference skips an iteration whose sample is empty (training.py:304-306): no ``zero_grad``, no learning-rate adjustment,
+no forward pass, no optimizer step, no logging.  Whether a batch drawn on the device is empty is known on the device only, so
+the decision is taken there (csrc/train_kernels.hip, include/dcn_hip.h section 13): ``TrainState.advance`` sets ``active`` and
+applies the schedule (``adjust_learning_rate``, :544-558, runs after the ``continue``: a decay boundary on an empty iteration is
+NOT applied), ``GuardedAdam.step`` updates nothing when the iteration is inactive, the batch-norm buffers the forward pass of
+such an iteration has changed are put back, and the log is a row of a device tensor instead of five ``.item()`` calls.  The
+host reads the state at save points only."""
+import ctypes
+import logging
+import os
+
+import numpy as np
+import torch
+
+from . import _lib, frames
+from .optim import GuardedAdam
+
+STATE_WORDS = 6                      # struct dcn_train_state: 48 bytes
+LOG_COLUMNS = 16                     # DCN_TRAIN_LOG_COLUMNS
+TERM_KEYS = ("loss", "match_loss", "masked_non_match_loss", "background_non_match_loss", "blind_non_match_loss")
+TYPE_NAMES = ("SINGLE_OBJECT_WITHIN_SCENE", "SINGLE_OBJECT_ACROSS_SCENE", "DIFFERENT_OBJECT", "MULTI_OBJECT",
+              "SYNTHETIC_MULTI_OBJECT")
+
+
+class StateSnapshot(object):
+    """One read of the state block and of the history rows written so far (``TrainState.read()``)."""
+
+    def __init__(self, words, history):
+        self.active = int(words[:1].view(np.int32)[0])
+        self.t = int(words[1])
+        self.lr = float(words[2:3].view(np.float64)[0])
+        f = words[3:4].view(np.float32)
+        self.step_size, self.bc2_sqrt = float(f[0]), float(f[1])
+        self.num_active, self.num_skipped = int(words[4]), int(words[5])
+        self.history = history          # float64 [rows, LOG_COLUMNS]
+
+
+class TrainState(object):
+    """The device-resident training state (struct dcn_train_state) and the history tensor behind it, in ONE device buffer so
+    that ``read()`` is one copy.  ``betas`` are Adam's: ``advance`` computes the bias corrections of the step it counts."""
+
+    def __init__(self, device, learning_rate, steps_between_learning_rate_decay, learning_rate_decay, betas=(0.9, 0.999),
+                 rows=1024):
+        self.device = torch.device(device)
+        self.steps_between_decay = int(steps_between_learning_rate_decay)
+        self.decay = float(learning_rate_decay)
+        self.betas = (float(betas[0]), float(betas[1]))
+        if self.steps_between_decay < 1:
+            raise ValueError("steps_between_learning_rate_decay must be >= 1")
+        self.capacity = max(int(rows), 1)
+        self.buf = torch.zeros(STATE_WORDS + self.capacity * LOG_COLUMNS, dtype=torch.int64, device=self.device)
+        _lib.require_device(self.buf)
+        self.rows = 0
+        self._bn = None
+        self.seed(0, float(learning_rate))
+
+    # ---- the block
+    def state_ptr(self):
+        return self.buf.data_ptr()
+
+    def _history_ptr(self):
+        return self.buf.data_ptr() + 8 * STATE_WORDS
+
+    def seed(self, t, lr):
+        """Set the Adam step count and the learning rate (a start, or a loaded checkpoint).  Stream-ordered, no read."""
+        self.buf[1:2].fill_(int(t))
+        self.buf[2:3].view(torch.float64).fill_(float(lr))
+
+    def _ensure_rows(self, rows):
+        if rows <= self.capacity:
+            return
+        cap = max(rows, 2 * self.capacity)
+        buf = torch.zeros(STATE_WORDS + cap * LOG_COLUMNS, dtype=torch.int64, device=self.device)
+        buf[:self.buf.numel()].copy_(self.buf)      # device to device, stream-ordered
+        self.buf, self.capacity = buf, cap
+
+    def _check_types(self, types):
+        if not torch.is_tensor(types) or types.dtype != torch.int32:
+            raise TypeError("types must be an int32 tensor (SampleBatch.type), got %s"
+                            % (types.dtype if torch.is_tensor(types) else type(types).__name__))
+        if types.device != self.buf.device:
+            raise ValueError("types is on %s, the training state on %s" % (types.device, self.buf.device))
+        if types.dim() != 1 or types.numel() < 1 or not types.is_contiguous():
+            raise ValueError("types must be a contiguous 1-D tensor with one entry per pair")
+
+    # ---- the iteration
+    def advance(self, types, iteration):
+        """Before the forward pass: active = any(types != -1); if active, the learning-rate decay of this iteration and Adam's
+        next step count with its bias corrections."""
+        self._check_types(types)
+        rc = _lib.get().dcn_train_advance(ctypes.c_void_p(self.state_ptr()), _lib.ptr(types), int(types.numel()), int(iteration),
+                                          self.steps_between_decay, self.decay, self.betas[0], self.betas[1], _lib.stream_ptr())
+        _lib.check(rc, "dcn_train_advance")
+
+    def _bn_tables(self, dcn):
+        bufs = list(dcn.buffers())
+        bn = self._bn
+        if bn is None or len(bn["bufs"]) != len(bufs) or any(a is not b for a, b in zip(bn["bufs"], bufs)) \
+                or any(s.shape != b.shape or s.dtype != b.dtype or s.device != b.device for s, b in zip(bn["snap"], bufs)):
+            for b in bufs:
+                if not b.is_contiguous() or (b.numel() * b.element_size()) % 4:
+                    raise ValueError("batch-norm buffers must be contiguous with a whole number of 32-bit words")
+            _lib.require_device(*bufs)
+            bn = self._bn = {"bufs": bufs, "snap": [torch.empty_like(b) for b in bufs],
+                             "bytes": (ctypes.c_int64 * len(bufs))(*[b.numel() * b.element_size() for b in bufs])}
+        n = len(bufs)
+        live = (ctypes.c_void_p * n)(*[b.data_ptr() for b in bufs])
+        snap = (ctypes.c_void_p * n)(*[s.data_ptr() for s in bn["snap"]])
+        return n, live, snap, bn["bytes"]
+
+    def snapshot_bn(self, dcn):
+        """Before the forward pass: copy every buffer of ``dcn`` (running_mean, running_var, num_batches_tracked)."""
+        n, live, snap, nbytes = self._bn_tables(dcn)
+        if n:
+            _lib.check(_lib.get().dcn_guarded_copy(n, snap, live, nbytes, None, 0, _lib.stream_ptr()), "dcn_guarded_copy")
+
+    def restore_bn_if_skipped(self, dcn):
+        """After the forward pass: put the snapshot back when the iteration is inactive (decided on the device)."""
+        n, live, snap, nbytes = self._bn_tables(dcn)
+        if n:
+            _lib.check(_lib.get().dcn_guarded_copy(n, live, snap, nbytes, ctypes.c_void_p(self.state_ptr()), 0,
+                                                   _lib.stream_ptr()), "dcn_guarded_copy")
+
+    def log(self, iteration, loss, terms, types):
+        """One history row: iteration, active, lr, num_valid, loss, (mean, count) of the five terms over the pairs whose type
+        composes them, type of the first non-empty pair."""
+        self._check_types(types)
+        B = int(types.numel())
+        if loss.dtype != torch.float32 or terms.dtype != torch.float32 or tuple(terms.shape) != (B, 5) \
+                or not terms.is_contiguous() or loss.numel() != 1:
+            raise ValueError("loss: one float32, terms: contiguous float32 [B, 5]")
+        _lib.require_device(loss, terms, types)
+        self._ensure_rows(self.rows + 1)
+        rc = _lib.get().dcn_train_log(ctypes.c_void_p(self._history_ptr()), self.rows, int(iteration),
+                                      ctypes.c_void_p(self.state_ptr()), _lib.ptr(loss.detach()), _lib.ptr(terms.detach()),
+                                      _lib.ptr(types), B, _lib.stream_ptr())
+        _lib.check(rc, "dcn_train_log")
+        self.rows += 1
+
+    # ---- the host's reads
+    def read(self):
+        """ONE copy to the host: the state block and the history rows so far -> StateSnapshot."""
+        words = self.buf[:STATE_WORDS + self.rows * LOG_COLUMNS].cpu().numpy()
+        return StateSnapshot(words[:STATE_WORDS], words[STATE_WORDS:].view(np.float64).reshape(self.rows, LOG_COLUMNS).copy())
+
+    def read_step_and_lr(self):
+        s = StateSnapshot(self.buf[:STATE_WORDS].cpu().numpy(), None)
+        return s.t, s.lr
+
+
+def empty_logging_dict():
+    """training.py:272-281"""
+    return {"train": {"iteration": [], "loss": [], "match_loss": [], "masked_non_match_loss": [],
+                      "background_non_match_loss": [], "blind_non_match_loss": [], "learning_rate": [],
+                      "different_object_non_match_loss": []},
+            "test": {"iteration": [], "loss": [], "match_loss": [], "non_match_loss": []}}
+
+
+def log_calls(row):
+    """What ``update_plots`` (training.py:353-413) does for one ACTIVE history row: ([(train key, value) appended to the
+    logging dict], [(tensorboard name, value) passed to log_value]), in the reference's order.  A term is there when its count
+    is > 0 (the type rule in place of ``is_zero_loss``); the data type is the first non-empty pair's (``metadata['type'][0]``).
+    As in the reference, only learning_rate, match_loss, masked_non_match_loss and background_non_match_loss reach the dict."""
+    lr, loss, dt = float(row[2]), float(row[4]), int(row[15])
+    mean = lambda k: float(row[5 + 2 * k])
+    has = lambda k: row[6 + 2 * k] > 0
+    appends, board = [("learning_rate", lr)], [("learning rate", lr)]
+    for k, name in ((1, "train match loss"), (2, "train masked non match loss"), (3, "train background non match loss")):
+        if has(k):
+            appends.append((TERM_KEYS[k], mean(k)))
+            board.append((name, mean(k)))
+    if has(4):
+        if dt == 0:
+            board.append(("train blind SINGLE_OBJECT_WITHIN_SCENE", mean(4)))
+        if dt == 2:
+            board.append(("train blind DIFFERENT_OBJECT", mean(4)))
+    if not 0 <= dt < len(TYPE_NAMES):
+        raise ValueError("unknown data type")
+    board.append(("train loss " + TYPE_NAMES[dt], loss))
+    if dt == 2:
+        board.append(("train different object", loss))
+    return appends, board
+
+
+def logging_dict_from_history(history):
+    d = empty_logging_dict()
+    for row in history:
+        if row[1] != 0:
+            for key, value in log_calls(row)[0]:
+                d["train"][key].append(value)
+    return d
+
+
+class StoreTrainer(object):
+    """The reference's ``run()`` over a ``FrameStore``.  ``config``: the reference's training.yaml dict (keys used, under
+    ``training``: learning_rate, learning_rate_decay, steps_between_learning_rate_decay, weight_decay, num_iterations,
+    batch_size, logging_rate, save_rate, data_type_probabilities and the sampling keys ``draw_training_batch`` reads).
+
+    Every iteration: draw_training_batch, TrainState.advance, zero_grad, batch-norm snapshot, forward_pair, get_loss_mixed,
+    backward, GuardedAdam.step(state), guarded batch-norm restore, TrainState.log.  Between save points the host reads nothing.
+
+    An INACTIVE iteration (every pair of the batch empty) still costs a forward and a backward pass: with the host out of the
+    loop there is no way to know before they are enqueued, and such iterations are rare.  Their effects are undone or withheld
+    on the device: parameters, moments, step count, learning rate and batch-norm buffers are as if the iteration had been
+    skipped, as the reference skips it.
+
+    The logging dict is the reference's: ``update_plots`` appends learning_rate, match_loss, masked_non_match_loss and
+    background_non_match_loss only (its other ``train`` lists stay empty); ``history`` holds every row in full."""
+
+    def __init__(self, dcn, pcl, store, config, *, optimizer=None, generator=None, host_rng=None, logging_dir=None,
+                 batch_size=None, per_pair_types=True, synthetic_multi_object=False):
+        t = config["training"]
+        self.dcn, self.pcl, self.store, self.config = dcn, pcl, store, config
+        self.generator, self.host_rng = generator, host_rng
+        self.per_pair_types, self.synthetic_multi_object = bool(per_pair_types), bool(synthetic_multi_object)
+        self.batch_size = int(batch_size if batch_size is not None else t["batch_size"])
+        self.num_iterations, self.save_rate = int(t["num_iterations"]), int(t["save_rate"])
+        self.logging_rate = int(t.get("logging_rate", 0) or 0)
+        if optimizer is None:
+            optimizer = GuardedAdam(dcn.parameters(), lr=float(t["learning_rate"]), weight_decay=float(t["weight_decay"]))
+        if not isinstance(optimizer, GuardedAdam):
+            raise TypeError("StoreTrainer needs a dcn_hip.optim.GuardedAdam (the update is skipped on the device), got %s"
+                            % type(optimizer).__name__)
+        self.optimizer = optimizer
+        self._refuse_distributed()
+        device = next(dcn.parameters()).device
+        self.state = TrainState(device, optimizer.param_groups[0]["lr"], t["steps_between_learning_rate_decay"],
+                                t["learning_rate_decay"], betas=optimizer.param_groups[0]["betas"],
+                                rows=self.num_iterations + 64)
+        optimizer.bind(self.state)
+        self.logging_dir = logging_dir
+        self.logging_dict = empty_logging_dict()
+        self.history = np.zeros((0, LOG_COLUMNS))
+        self._board, self._board_rows = None, 0
+        self.last = None                     # (loss, terms, num_valid, SampleBatch) of the latest iteration, on the device
+
+    def _refuse_distributed(self):
+        owners = [m for m in self.dcn.modules() if getattr(m, "_flat_grad_owner", None) is not None]
+        if getattr(self.optimizer, "_flat_gradients", None) is not None or owners:
+            raise NotImplementedError("StoreTrainer: dcn_hip.distributed gradients are attached; a skip decision that is "
+                                      "consistent across ranks is not implemented")
+
+    # ---- one iteration: nothing here reads the device
+    def iteration(self, iteration):
+        B = self.batch_size
+        sb, _, _ = frames.draw_training_batch(self.store, B, self.config, generator=self.generator, host_rng=self.host_rng,
+                                              per_pair_types=self.per_pair_types,
+                                              synthetic_multi_object=self.synthetic_multi_object)
+        return self.step_on_batch(sb, iteration)
+
+    def step_on_batch(self, sb, iteration):
+        from dense_correspondence.loss_functions import loss_composer
+        B = int(sb.type.numel())
+        dcn, state = self.dcn, self.state
+        state.advance(sb.type, iteration)
+        self.optimizer.zero_grad()
+        state.snapshot_bn(dcn)
+        ya, yb = dcn.forward_pair(sb.input_a, sb.input_b)
+        loss, terms, _, num_valid = loss_composer.get_loss_mixed(self.pcl, dcn.process_network_output(ya, B),
+                                                                 dcn.process_network_output(yb, B), sb.device_lists())
+        loss.backward()
+        self.optimizer.step(state)
+        state.restore_bn_if_skipped(dcn)
+        state.log(iteration, loss, terms, sb.type)
+        self.last = (loss.detach(), terms, num_valid, sb)
+        return loss
+
+    # ---- the host's side: save points and the end
+    def read_log(self):
+        snap = self.state.read()
+        self.history = snap.history
+        self.logging_dict = logging_dict_from_history(snap.history)
+        if self.logging_dir is not None:
+            if self._board is None:
+                import tensorboard_logger
+                self._board = tensorboard_logger.Logger(os.path.join(self.logging_dir, "tensorboard"))
+            for row in snap.history[self._board_rows:]:
+                if row[1] != 0:
+                    for name, value in log_calls(row)[1]:
+                        self._board.log_value(name, value, int(row[0]))
+        self._board_rows = len(snap.history)
+        return snap
+
+    def save_network(self, iteration, snap=None, logging_dict=None):
+        """training.py:501-521: %06d.pth, %06d.pth.opt and, with a logging dict, %06d_log_history.yaml and loss.yaml."""
+        from dense_correspondence_manipulation.utils import utils
+        os.makedirs(self.logging_dir, exist_ok=True)
+        f = os.path.join(self.logging_dir, utils.getPaddedString(iteration, width=6) + ".pth")
+        torch.save(self.dcn.state_dict(), f)
+        torch.save(self.optimizer.state_dict(known=(snap.t, snap.lr) if snap is not None else None), f + ".opt")
+        if logging_dict is not None:
+            utils.saveToYaml(logging_dict, os.path.join(self.logging_dir,
+                                                        utils.getPaddedString(iteration, width=6) + "_log_history.yaml"))
+            current = {}
+            for key in ("train", "test"):
+                current[key] = {field: (vec[-1] if len(vec) > 0 else -1) for field, vec in logging_dict[key].items()}
+            utils.saveToYaml(current, os.path.join(self.logging_dir, "loss.yaml"))
+
+    def save_configs(self):
+        """training.py:525-532: training.yaml, with the network's own config under dense_correspondence_network when the
+        dict given has none (DenseCorrespondenceNetwork.from_model_folder reads it from there)."""
+        from dense_correspondence_manipulation.utils import utils
+        os.makedirs(self.logging_dir, exist_ok=True)
+        cfg = dict(self.config)
+        if "dense_correspondence_network" not in cfg and getattr(self.dcn, "config", None) is not None:
+            cfg["dense_correspondence_network"] = {k: v for k, v in self.dcn.config.items()
+                                                   if k not in ("model_param_file", "path_to_network_params_folder",
+                                                                "model_param_filename_tail")}
+        utils.saveToYaml(cfg, os.path.join(self.logging_dir, "training.yaml"))
+
+    def run(self, loss_current_iteration=0):
+        """The loop of training.py:290-456 from iteration ``loss_current_iteration`` + 1.  A save point is ``iteration %
+        save_rate == 0``: one read of the state; nothing is saved when that iteration was inactive (the reference has
+        ``continue``d past its save).  The end follows the reference's ``>``: after ``num_iterations`` + start iterations the
+        host reads ``active`` once per further iteration and stops, with a final save, at the first active one.
+        -> the logging dict."""
+        self._refuse_distributed()
+        start = int(loss_current_iteration)
+        max_num_iterations = self.num_iterations + start
+        self.dcn.train()
+        if self.logging_dir is not None:
+            self.save_configs()
+            if start == 0:
+                self.save_network(0)
+        it = start
+        while True:
+            it += 1
+            self.iteration(it)
+            snap = None
+            if self.logging_dir is not None and self.save_rate > 0 and it % self.save_rate == 0:
+                snap = self.read_log()
+                if snap.active:
+                    self.save_network(it, snap, self.logging_dict)
+            if self.logging_rate and it % self.logging_rate == 0:
+                logging.info("Training on iteration %d of %d" % (it, max_num_iterations))
+            if it > max_num_iterations:
+                saved = snap is not None
+                if snap is None:
+                    snap = self.read_log()      # the one read of this iteration: `active`, and the rows for the final save
+                if not snap.active:
+                    continue
+                logging.info("Finished testing after %d iterations" % max_num_iterations)
+                if self.logging_dir is not None and not saved:
+                    self.save_network(it, snap, self.logging_dict)
+                return self.logging_dict
