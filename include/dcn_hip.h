@@ -1156,6 +1156,48 @@ int dcn_guarded_copy(int n, void* const* dst, const void* const* src, const int6
 int dcn_train_log(double* history, int64_t row, int64_t iteration, const struct dcn_train_state* state, const float* loss,
                   const float* terms, const int32_t* types, int B, void* stream);
 
+/* =====================================================================================================
+ * 14. Evaluation curves -- what the reference does with a column of an evaluation table:
+ *     DenseCorrespondenceEvaluationPlotter.make_cdf_plot and compute_area_above_curve
+ *     (dense_correspondence/evaluation/evaluation.py:2658-2674, :2844-2863): the empirical CDF of the column over num_bins
+ *     bins (scipy.stats.cumfreq with defaultreallimits=None) and the area above it, the number stats.yaml keeps as
+ *     norm_diff_3d_area_above_curve (:2953-2975).
+ *
+ *     values float64 [c][ld]: curve k reads values[k * ld + r], r < rows <= ld.  Row r belongs to the table iff row_pair ==
+ *     NULL or row_pair[r] >= 0 (the tables of sections 9 to 11 mark rows past the end, and cross-scene rows without a result,
+ *     with -1 and NaN); a row that does not belong is neither counted nor counted as dropped.  drop_nan uint8 [c]: non-zero
+ *     drops and counts the NaNs of rows that belong (dropna()); zero makes a NaN an error of that curve (DCN_CURVE_NAN).
+ *
+ *     In float64, every operation rounded on its own (no fma): n = values kept, mn, mx their minimum and maximum;
+ *     s = (mx - mn) / (2. * (num_bins - 1.)); lowerlimit = mn - s; upper = mx + s; the histogram's range is (lowerlimit,
+ *     upper), widened to (lowerlimit - 0.5, upper + 0.5) when the two are equal (lowerlimit is reported unwidened, binsize
+ *     comes from the widened edges); edge[i] = i * step + first with step = (last - first) / num_bins, edge[num_bins] = last
+ *     (np.linspace); binsize = edge[1] - edge[0]; a value is in bin i with edge[i] <= x < edge[i + 1], the last bin closed on
+ *     the right -- found as numpy does, by division and a correction by one against the edges.
+ *       cumcount int64 [c][num_bins]   running sum of the bin counts
+ *       cdf float64 [c][num_bins]      cumcount[i] * (1.0 / n)
+ *       summary float64 [c][DCN_CURVE_SUMMARY_DOUBLES]:
+ *                                      0 n, 1 NaNs dropped, 2 mn, 3 mx, 4 lowerlimit, 5 binsize,
+ *                                      6 area_above_curve = binsize * sum_i (1 - cdf[i]), 7 the curve's flag bits
+ *       status int32 [1]               the OR of all curves' flag bits (written, not accumulated)
+ *     The sum of the area runs in one fixed order (a butterfly over each 64 bins, the groups of 64 in order) and the counts are
+ *     integer atomics in LDS: the outputs are the same bit for bit from run to run.  A flagged curve has cumcount 0 and NaN in
+ *     cdf, lowerlimit, binsize and area_above_curve (mn and mx NaN too unless the flag is DCN_CURVE_NONFINITE); the other
+ *     curves of the launch are not affected.  DCN_CURVE_NONFINITE also covers finite values whose range is not representable
+ *     (mx - mn overflows, or +-0.5 does not widen it).  A bin holds fewer than 2^31 values.
+ *     One workgroup per curve (rows in a strided loop: no bound on rows), one launch for all curves after a 4-byte fill of
+ *     status, no workspace, no host synchronisation.  1 <= c <= 64, 2 <= num_bins <= 4096, 0 <= rows <= ld; rows == 0 is legal
+ *     (every curve DCN_CURVE_EMPTY) and then values may be NULL.
+ * ===================================================================================================== */
+#define DCN_CURVE_SUMMARY_DOUBLES 8
+#define DCN_CURVE_EMPTY 1       /* no value left: the reference divides by len(data) == 0 */
+#define DCN_CURVE_NAN 2         /* a NaN met with drop_nan off: numpy refuses the range */
+#define DCN_CURVE_NONFINITE 4   /* +-inf among the values: numpy refuses the range */
+int dcn_eval_curves(int c, int64_t rows, int64_t ld, const double* values /* [c][ld] */,
+                    const int32_t* row_pair /* [rows] or NULL */, const uint8_t* drop_nan /* [c] */,
+                    int num_bins, int64_t* cumcount /* [c][num_bins] */, double* cdf /* [c][num_bins] */,
+                    double* summary /* [c][8] */, int32_t* status /* [1], OR of all curves */, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -241,6 +241,7 @@ SYMBOLS = {
                                       ctypes.c_double, ctypes.c_double, ctypes.c_double, c_void_p, c_void_p]),
     "dcn_guarded_copy": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
     "dcn_train_log": (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
+    "dcn_eval_curves": (c_int, [c_int, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_int] + [c_void_p] * 5),
 }
 
 ERRORS = {-1: "DCN_E_INVALID (bad argument)", -2: "DCN_E_LAUNCH (kernel launch failed)",

@@ -7,7 +7,12 @@ the decision is taken there (csrc/train_kernels.hip, include/dcn_hip.h section 1
 applies the schedule (``adjust_learning_rate``, :544-558, runs after the ``continue``: a decay boundary on an empty iteration is
 NOT applied), ``GuardedAdam.step`` updates nothing when the iteration is inactive, the batch-norm buffers the forward pass of
 such an iteration has changed are put back, and the log is a row of a device tensor instead of five ``.item()`` calls.  The
-host reads the state at save points only."""
+host reads the state at save points only.
+
+``Validation`` is what the reference's ``compute_test_loss`` hook (training.py:427-441; dead code there) was for: every
+``rate`` iterations a held-out store is evaluated (``evaluate.evaluate_frame_pairs``) and reduced on the device to the
+reference's curves (``evaluate.evaluation_curves``, csrc/curve_kernels.hip): eight numbers per curve in a row of a second
+device history, read with the log at save points."""
 import ctypes
 import logging
 import os
@@ -15,7 +20,7 @@ import os
 import numpy as np
 import torch
 
-from . import _lib, frames
+from . import _lib, evaluate, frames
 from .optim import GuardedAdam
 
 STATE_WORDS = 6                      # struct dcn_train_state: 48 bytes
@@ -185,6 +190,100 @@ def log_calls(row):
     return appends, board
 
 
+VALIDATION_HEAD = 4                  # a validation row: iteration, active, the table's status, the curves' status, [C][8]
+
+
+def validation_key(field):
+    """The logging dict's key for a field's area above the curve; stats.yaml's name for ``norm_diff_pred_3d``"""
+    return "norm_diff_3d_area_above_curve" if field == "norm_diff_pred_3d" else field + "_area_above_curve"
+
+
+class Validation(object):
+    """A held-out ``FrameStore`` evaluated while training (``StoreTrainer(..., validation=...)``): after iteration ``it`` with
+    ``it % rate == 0 and it > after`` (the reference's condition for its test loss, training.py:428), ``num_image_pairs`` pairs
+    by ``evaluate.choose_pairs`` with this object's OWN ``host_rng``, ``evaluate.evaluate_frame_pairs`` with its OWN
+    ``generator`` (eval mode; ``dcn.training`` and the batch-norm buffers are left as found) and ``evaluate.evaluation_curves``
+    of ``fields`` over ``num_bins`` bins, the summaries written straight into the next row of ``history``: float64
+    [rows, 4 + 8 C] on the device -- iteration, ``active`` of that iteration (copied from the training state on the device),
+    the table's status word, the curves' status word, then evaluate.CURVE_SUMMARY per field.  Nothing is read back; the
+    training's generator and ``host_rng`` are not touched."""
+
+    def __init__(self, store, rate, num_image_pairs=25, num_matches_per_image_pair=100, fields=evaluate.CURVE_FIELDS,
+                 num_bins=100, after=5, generator=None, host_rng=None, batch_pairs=8):
+        self.store, self.rate, self.after = store, int(rate), int(after)
+        self.num_image_pairs, self.num_matches = int(num_image_pairs), int(num_matches_per_image_pair)
+        self.fields, self.num_bins, self.batch_pairs = tuple(fields), int(num_bins), int(batch_pairs)
+        self.generator, self.host_rng = generator, host_rng
+        if self.rate < 1:
+            raise ValueError("Validation: rate must be >= 1, got %d" % self.rate)
+        if not 1 <= self.num_image_pairs <= 1024:
+            raise ValueError("Validation: num_image_pairs must be 1 .. 1024, got %d" % self.num_image_pairs)
+        unknown = [f for f in self.fields if f not in evaluate.COLUMNS]
+        if unknown or not 1 <= len(self.fields) <= evaluate.MAX_CURVES:
+            raise ValueError("Validation: 1 .. %d fields out of evaluate.COLUMNS, got %s" % (evaluate.MAX_CURVES, self.fields))
+        if not 2 <= self.num_bins <= evaluate.MAX_CURVE_BINS:
+            raise ValueError("Validation: num_bins must be 2 .. %d, got %d" % (evaluate.MAX_CURVE_BINS, self.num_bins))
+        self.width = VALIDATION_HEAD + len(self.fields) * len(evaluate.CURVE_SUMMARY)
+        self.history = torch.zeros((16, self.width), dtype=torch.float64, device=store.device)
+        self.rows = 0
+
+    def due(self, iteration):
+        return iteration % self.rate == 0 and iteration > self.after
+
+    def _next_row(self):
+        if self.rows == self.history.shape[0]:
+            grown = torch.zeros((2 * self.rows, self.width), dtype=torch.float64, device=self.history.device)
+            grown[:self.rows].copy_(self.history)       # device to device, stream-ordered
+            self.history = grown
+        return self.history[self.rows]
+
+    def run(self, dcn, state, iteration):
+        """One pass after iteration ``iteration`` of the training ``state`` (a TrainState) -> the EvalCurves, on the device."""
+        chosen = evaluate.choose_pairs(self.store, self.num_image_pairs, self.host_rng)
+        row = self._next_row()
+        row[0:1].fill_(float(iteration))
+        row[1:2].copy_(state.buf[:1].view(torch.int32)[:1])          # struct dcn_train_state.active, on the device
+        if chosen.shape[0] == 0:                 # no two frames far enough apart: a table without rows, every curve empty
+            summary = row[VALIDATION_HEAD:].view(len(self.fields), len(evaluate.CURVE_SUMMARY))
+            summary.fill_(float("nan"))
+            summary[:, :2].fill_(0.0)
+            summary[:, 7].fill_(float(evaluate.CURVE_EMPTY))
+            row[2:3].fill_(0.0)
+            row[3:4].fill_(float(evaluate.CURVE_EMPTY))
+            self.rows += 1
+            return None
+        table = evaluate.evaluate_frame_pairs(dcn, self.store, chosen, self.num_matches, generator=self.generator,
+                                              batch_pairs=self.batch_pairs)
+        C = len(self.fields)
+        curves = evaluate.evaluation_curves(table, self.fields, self.num_bins,
+                                            out_summary=row[VALIDATION_HEAD:].view(C, len(evaluate.CURVE_SUMMARY)))
+        row[2:3].copy_(table.status)
+        row[3:4].copy_(curves.status)
+        self.rows += 1
+        return curves
+
+    def read(self):
+        """ONE copy to the host: the rows so far, float64 [rows, 4 + 8 C]"""
+        return self.history[:self.rows].cpu().numpy()
+
+    def logging_dict(self, rows):
+        """``logging_dict["validation"]`` of the rows read: the iterations that counted (``active``), per field the area above
+        the curve and the number of values behind it"""
+        d = {"iteration": []}
+        for f in self.fields:
+            d[validation_key(f)] = []
+            d[f + "_count"] = []
+        for row in rows:
+            if row[1] == 0:
+                continue
+            d["iteration"].append(int(row[0]))
+            for k, f in enumerate(self.fields):
+                s = row[VALIDATION_HEAD + 8 * k:VALIDATION_HEAD + 8 * (k + 1)]
+                d[validation_key(f)].append(float(s[6]))
+                d[f + "_count"].append(int(s[0]))
+        return d
+
+
 def logging_dict_from_history(history):
     d = empty_logging_dict()
     for row in history:
@@ -211,7 +310,7 @@ class StoreTrainer(object):
     background_non_match_loss only (its other ``train`` lists stay empty); ``history`` holds every row in full."""
 
     def __init__(self, dcn, pcl, store, config, *, optimizer=None, generator=None, host_rng=None, logging_dir=None,
-                 batch_size=None, per_pair_types=True, synthetic_multi_object=False):
+                 batch_size=None, per_pair_types=True, synthetic_multi_object=False, validation=None):
         t = config["training"]
         self.dcn, self.pcl, self.store, self.config = dcn, pcl, store, config
         self.generator, self.host_rng = generator, host_rng
@@ -236,6 +335,17 @@ class StoreTrainer(object):
         self.history = np.zeros((0, LOG_COLUMNS))
         self._board, self._board_rows = None, 0
         self.last = None                     # (loss, terms, num_valid, SampleBatch) of the latest iteration, on the device
+        if validation is not None:
+            if not isinstance(validation, Validation):
+                raise TypeError("validation must be a dcn_hip.train.Validation, got %s" % type(validation).__name__)
+            if [int(validation.store.h), int(validation.store.w)] != [int(v) for v in dcn.image_shape]:
+                raise ValueError("validation store of %d x %d images, network of %s" % (validation.store.h, validation.store.w,
+                                                                                      list(dcn.image_shape)))
+            if torch.device(validation.store.device).type != device.type:
+                raise ValueError("validation store on %s, network on %s" % (validation.store.device, device))
+        self.validation = validation
+        self.validation_history = None       # float64 [rows, 4 + 8 C] as of the latest read_log()
+        self._validation_board_rows = 0
 
     def _refuse_distributed(self):
         owners = [m for m in self.dcn.modules() if getattr(m, "_flat_grad_owner", None) is not None]
@@ -268,11 +378,22 @@ class StoreTrainer(object):
         self.last = (loss.detach(), terms, num_valid, sb)
         return loss
 
+    def validate(self, iteration):
+        """The validation pass of ``iteration`` (run() calls it when ``validation.due(iteration)``): nothing here reads the
+        device.  An iteration the device finds inactive still gets its pass -- the host cannot know -- and its row carries
+        ``active == 0``."""
+        if self.validation is None:
+            raise ValueError("StoreTrainer: no validation configured")
+        return self.validation.run(self.dcn, self.state, iteration)
+
     # ---- the host's side: save points and the end
     def read_log(self):
         snap = self.state.read()
         self.history = snap.history
         self.logging_dict = logging_dict_from_history(snap.history)
+        if self.validation is not None:
+            self.validation_history = self.validation.read()       # one more copy at a save point
+            self.logging_dict["validation"] = self.validation.logging_dict(self.validation_history)
         if self.logging_dir is not None:
             if self._board is None:
                 import tensorboard_logger
@@ -281,7 +402,15 @@ class StoreTrainer(object):
                 if row[1] != 0:
                     for name, value in log_calls(row)[1]:
                         self._board.log_value(name, value, int(row[0]))
+            if self.validation is not None:
+                for row in self.validation_history[self._validation_board_rows:]:
+                    if row[1] != 0:
+                        for k, f in enumerate(self.validation.fields):
+                            self._board.log_value("validation %s area above curve" % f,
+                                                  float(row[VALIDATION_HEAD + 8 * k + 6]), int(row[0]))
         self._board_rows = len(snap.history)
+        if self.validation is not None:
+            self._validation_board_rows = len(self.validation_history)
         return snap
 
     def save_network(self, iteration, snap=None, logging_dict=None):
@@ -295,7 +424,7 @@ class StoreTrainer(object):
             utils.saveToYaml(logging_dict, os.path.join(self.logging_dir,
                                                         utils.getPaddedString(iteration, width=6) + "_log_history.yaml"))
             current = {}
-            for key in ("train", "test"):
+            for key in ("train", "test"):        # (loss.yaml as the reference writes it: no validation key)
                 current[key] = {field: (vec[-1] if len(vec) > 0 else -1) for field, vec in logging_dict[key].items()}
             utils.saveToYaml(current, os.path.join(self.logging_dir, "loss.yaml"))
 
@@ -329,6 +458,8 @@ class StoreTrainer(object):
         while True:
             it += 1
             self.iteration(it)
+            if self.validation is not None and self.validation.due(it):
+                self.validate(it)
             snap = None
             if self.logging_dir is not None and self.save_rate > 0 and it % self.save_rate == 0:
                 snap = self.read_log()
