@@ -29,6 +29,7 @@
 
 namespace {
 
+using dcn::align256;
 using dcn::check_offsets_kernel;
 using dcn::order_key;
 using dcn::pair_rows;
@@ -378,8 +379,6 @@ __global__ void __launch_bounds__(256) pair_finish_kernel(const unsigned long lo
     best_uv[max_rows + r] = i / w;
     row_pair[r] = p;
 }
-
-inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
 
 inline bool shape_ok(int p, int h, int w, int d) {
     return p >= 1 && p <= kMaxPairs && h >= 1 && w >= 1 && (int64_t)h * w < ((int64_t)1 << 31) && d >= 1 && d <= kMaxD;

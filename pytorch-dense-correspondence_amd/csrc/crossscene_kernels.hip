@@ -27,7 +27,6 @@
 
 namespace {
 
-using dcn::check_offsets_kernel;
 using dcn::clip_round;
 using dcn::pair_rows;
 
@@ -337,8 +336,6 @@ __global__ void __launch_bounds__(256) group_rows_kernel(GroupRows a) {
                     a.gt_d[r], a.count[r], a.count[R + r], a.dist_sum[r], a.dist_sum[R + r], a.mask_pixels[g], a.hw, w);
 }
 
-inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
-
 }  // namespace
 
 extern "C" int dcn_reproject_pixels(int v, const dcn_frame_store* store, const float* kcam, const int32_t* requests,
@@ -368,11 +365,7 @@ extern "C" int dcn_reproject_pixels(int v, const dcn_frame_store* store, const f
     return dcn::check_launch();
 }
 
-// best [2][R] u64 | dist_sum [2][R] u64 | gt_d [R] float | offsets_bad int32
-extern "C" size_t dcn_match_statistics_groups_workspace(int64_t max_rows) {
-    const size_t r = (size_t)(max_rows > 0 ? max_rows : 1);
-    return 2 * align256(r * 2 * sizeof(unsigned long long)) + align256(r * sizeof(float)) + 256;
-}
+extern "C" size_t dcn_match_statistics_groups_workspace(int64_t max_rows) { return dcn::stats_workspace_bytes(max_rows); }
 
 namespace {
 
@@ -391,24 +384,13 @@ int run_groups(bool wide, int64_t strip_pixels, int g, int h, int w, int d, cons
     const int row_blocks = dcn::ceil_div64(max_group_rows, kWR);
     if (wide && (strip_pixels < 0 || row_blocks > 65535)) return DCN_E_INVALID;
     hipStream_t st = (hipStream_t)stream;
-    char* ws = (char*)workspace;
-    const size_t R = (size_t)max_rows;
     GroupStats a;
-    a.best = (unsigned long long*)ws;
-    a.dist_sum = (unsigned long long*)(ws + align256(R * 2 * sizeof(unsigned long long)));
-    a.gt_d = (float*)((char*)a.dist_sum + align256(R * 2 * sizeof(unsigned long long)));
-    a.count = closer;
-    int32_t* flag = (int32_t*)((char*)a.gt_d + align256(R * sizeof(float)));
-    a.offsets_bad = flag;
-    int rc = dcn::fill_bytes_async(a.best, 0xFF, R * 2 * sizeof(unsigned long long), st);
-    if (rc == DCN_OK) rc = dcn::fill_bytes_async(closer, 0, R * 2 * sizeof(int32_t), st);
-    if (rc == DCN_OK) rc = dcn::fill_bytes_async(a.dist_sum, 0, R * 2 * sizeof(unsigned long long), st);
-    if (rc == DCN_OK) rc = dcn::fill_bytes_async(a.gt_d, 0, align256(R * sizeof(float)), st);
-    if (rc == DCN_OK) rc = dcn::fill_bytes_async(mask_pixels, 0, (size_t)g * sizeof(int32_t), st);
-    if (rc == DCN_OK) rc = dcn::fill_bytes_async(status, 0, sizeof(int32_t), st);
-    if (rc == DCN_OK) rc = dcn::fill_bytes_async(flag, 0, sizeof(int32_t), st);
+    int32_t* flag;
+    const int rc = dcn::prepare_stats_scratch(workspace, max_rows, closer, mask_pixels, g, status, offsets, st, a.best,
+                                              a.dist_sum, a.gt_d, flag);
     if (rc != DCN_OK) return rc;
-    hipLaunchKernelGGL(check_offsets_kernel, dim3(dcn::ceil_div(g, 256)), dim3(256), 0, st, offsets, g, max_rows, flag, status);
+    a.count = closer;
+    a.offsets_bad = flag;
     a.res_b = res_b;
     a.mask_b = mask_b;
     a.queries = queries;
@@ -439,28 +421,10 @@ int run_groups(bool wide, int64_t strip_pixels, int g, int h, int w, int d, cons
             ww.strip = dcn::ceil_div64(sp, kWT) * kWT;
         }
         const dim3 grid((unsigned)dcn::ceil_div64(hw, ww.strip), (unsigned)row_blocks, (unsigned)g), block(kWR);
-#define DCN_WS(DT) hipLaunchKernelGGL((wide_stats_kernel<DT>), grid, block, 0, st, ww)
-        switch (d) {
-            case 3: DCN_WS(3); break;
-            case 4: DCN_WS(4); break;
-            case 8: DCN_WS(8); break;
-            case 16: DCN_WS(16); break;
-            case 32: DCN_WS(32); break;
-            default: DCN_WS(0); break;
-        }
-#undef DCN_WS
+        DCN_LAUNCH_FOR_D(d, wide_stats_kernel, grid, block, st, ww);
     } else {
         const dim3 grid((unsigned)dcn::ceil_div64(hw, kMT), (unsigned)g), block(kMT);
-#define DCN_GS(DT) hipLaunchKernelGGL((group_stats_kernel<DT>), grid, block, 0, st, a)
-        switch (d) {
-            case 3: DCN_GS(3); break;
-            case 4: DCN_GS(4); break;
-            case 8: DCN_GS(8); break;
-            case 16: DCN_GS(16); break;
-            case 32: DCN_GS(32); break;
-            default: DCN_GS(0); break;
-        }
-#undef DCN_GS
+        DCN_LAUNCH_FOR_D(d, group_stats_kernel, grid, block, st, a);
     }
     GroupRows b;
     b.depth_b = depth_b;

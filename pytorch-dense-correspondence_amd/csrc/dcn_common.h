@@ -79,4 +79,18 @@ inline int check_launch() { return hipGetLastError() == hipSuccess ? DCN_OK : DC
 __host__ __device__ inline int64_t ceil_div64(int64_t a, int64_t b) { return (a + b - 1) / b; }
 __host__ __device__ inline int ceil_div(int a, int b) { return (a + b - 1) / b; }
 
+inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }   // (the parts of a carved workspace start 256-aligned)
+
 }  // namespace dcn
+
+// Launches the instance of the kernel template K<int DT> for descriptor dimension d: the dimensions that have an instance of
+// their own, every other one by the generic K<0>, which reads D at run time.
+#define DCN_LAUNCH_FOR_D(d, K, grid, block, st, ...)                                       \
+    switch (d) {                                                                           \
+        case 3: hipLaunchKernelGGL((K<3>), grid, block, 0, st, __VA_ARGS__); break;        \
+        case 4: hipLaunchKernelGGL((K<4>), grid, block, 0, st, __VA_ARGS__); break;        \
+        case 8: hipLaunchKernelGGL((K<8>), grid, block, 0, st, __VA_ARGS__); break;        \
+        case 16: hipLaunchKernelGGL((K<16>), grid, block, 0, st, __VA_ARGS__); break;      \
+        case 32: hipLaunchKernelGGL((K<32>), grid, block, 0, st, __VA_ARGS__); break;      \
+        default: hipLaunchKernelGGL((K<0>), grid, block, 0, st, __VA_ARGS__); break;       \
+    }

@@ -230,7 +230,7 @@ __global__ void __launch_bounds__(kMaxD) stats_combine_kernel(const float* __res
     if (c == 0) *used = count;
 }
 
-inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
+using dcn::align256;
 
 inline bool shape_ok(int n, int h, int w, int d) {
     return n >= 1 && n <= 65535 && h >= 1 && w >= 1 && (int64_t)h * w < ((int64_t)1 << 31) && d >= 1 && d <= kMaxD;

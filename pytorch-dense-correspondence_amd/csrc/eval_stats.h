@@ -9,8 +9,10 @@
 //                                     load: thousands of workgroups target the same few words and almost every key loses.
 //   finish_row / empty_row            one row of the table from its keys, counts and sums; the depth / 3D half
 //                                     (evaluation.py:1102-1135, :1148-1164) in float64 from the row's fp32 camera row.
+//   stats_workspace_bytes / prepare_stats_scratch   (host) the workspace both entries carve, its fills and the offsets check.
 #pragma once
 #include "dcn_common.h"
+#include "eval_rows.h"
 
 namespace dcn {
 
@@ -242,6 +244,37 @@ __device__ __forceinline__ void finish_row(const EvalRowOut& o, int64_t r, int p
     o.col[(int64_t)DCN_EVAL_COL_NORM_DIFF_GROUND_TRUTH_3D * R + r] = validb ? eval_norm3(pb, pa) : nan;
     o.col[(int64_t)DCN_EVAL_COL_NORM_DIFF_PRED_3D * R + r] = (validb && valid0) ? eval_norm3(pb, p0) : nan;
     o.col[(int64_t)DCN_EVAL_COL_NORM_DIFF_PRED_3D_MASKED * R + r] = (validb && valid1) ? eval_norm3(pb, p1) : nan;
+}
+
+// ---- the host half: the scratch both entries carve from their workspace
+// best [2][R] u64 | dist_sum [2][R] u64 | gt_d [R] float | offsets_bad int32
+inline size_t stats_workspace_bytes(int64_t max_rows) {
+    const size_t r = (size_t)(max_rows > 0 ? max_rows : 1);
+    return 2 * align256(r * 2 * sizeof(unsigned long long)) + align256(r * sizeof(float)) + 256;
+}
+
+// Carves `workspace` into best, dist_sum, gt_d and flag, clears them and what the search accumulates into (closer [2][R],
+// mask_pixels [groups], status) and launches check_offsets_kernel over the `groups` row lists
+inline int prepare_stats_scratch(void* workspace, int64_t max_rows, int32_t* closer, int32_t* mask_pixels, int groups,
+                                 int32_t* status, const int64_t* offsets, hipStream_t st, unsigned long long*& best,
+                                 unsigned long long*& dist_sum, float*& gt_d, int32_t*& flag) {
+    char* ws = (char*)workspace;
+    const size_t R = (size_t)max_rows;
+    best = (unsigned long long*)ws;
+    dist_sum = (unsigned long long*)(ws + align256(R * 2 * sizeof(unsigned long long)));
+    gt_d = (float*)((char*)dist_sum + align256(R * 2 * sizeof(unsigned long long)));
+    flag = (int32_t*)((char*)gt_d + align256(R * sizeof(float)));
+    int rc = fill_bytes_async(best, 0xFF, R * 2 * sizeof(unsigned long long), st);
+    if (rc == DCN_OK) rc = fill_bytes_async(closer, 0, R * 2 * sizeof(int32_t), st);
+    if (rc == DCN_OK) rc = fill_bytes_async(dist_sum, 0, R * 2 * sizeof(unsigned long long), st);
+    if (rc == DCN_OK) rc = fill_bytes_async(gt_d, 0, align256(R * sizeof(float)), st);
+    if (rc == DCN_OK) rc = fill_bytes_async(mask_pixels, 0, (size_t)groups * sizeof(int32_t), st);
+    if (rc == DCN_OK) rc = fill_bytes_async(status, 0, sizeof(int32_t), st);
+    if (rc == DCN_OK) rc = fill_bytes_async(flag, 0, sizeof(int32_t), st);
+    if (rc != DCN_OK) return rc;
+    hipLaunchKernelGGL(check_offsets_kernel, dim3(ceil_div(groups, 256)), dim3(256), 0, st, offsets, groups, max_rows, flag,
+                       status);
+    return DCN_OK;
 }
 
 }  // namespace dcn

@@ -19,7 +19,6 @@
 
 namespace {
 
-using dcn::check_offsets_kernel;
 using dcn::clip_round;
 using dcn::pair_rows;
 
@@ -153,15 +152,9 @@ __global__ void __launch_bounds__(256) pair_rows_kernel(PairRows a) {
                     a.dist_sum[r], a.dist_sum[R + r], a.mask_pixels[p], a.hw, w);
 }
 
-inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
-
 }  // namespace
 
-// best [2][R] u64 | dist_sum [2][R] u64 | gt_d [R] float | offsets_bad int32
-extern "C" size_t dcn_match_statistics_pairs_workspace(int64_t max_rows) {
-    const size_t r = (size_t)(max_rows > 0 ? max_rows : 1);
-    return 2 * align256(r * 2 * sizeof(unsigned long long)) + align256(r * sizeof(float)) + 256;
-}
+extern "C" size_t dcn_match_statistics_pairs_workspace(int64_t max_rows) { return dcn::stats_workspace_bytes(max_rows); }
 
 extern "C" int dcn_match_statistics_pairs(int p, int h, int w, int d, const float* res_a, const float* res_b,
                                           const uint8_t* mask_b, const uint16_t* depth_a, const uint16_t* depth_b,
@@ -176,24 +169,13 @@ extern "C" int dcn_match_statistics_pairs(int p, int h, int w, int d, const floa
         max_pair_rows < 1 || !columns || !is_valid || !pred_uv || !closer || !row_pair || !mask_pixels || !status || !workspace)
         return DCN_E_INVALID;
     hipStream_t st = (hipStream_t)stream;
-    char* ws = (char*)workspace;
-    const size_t R = (size_t)max_rows;
     PairStats a;
-    a.best = (unsigned long long*)ws;
-    a.dist_sum = (unsigned long long*)(ws + align256(R * 2 * sizeof(unsigned long long)));
-    a.gt_d = (float*)((char*)a.dist_sum + align256(R * 2 * sizeof(unsigned long long)));
-    a.count = closer;
-    int32_t* flag = (int32_t*)((char*)a.gt_d + align256(R * sizeof(float)));
-    a.offsets_bad = flag;
-    int rc = dcn::fill_bytes_async(a.best, 0xFF, R * 2 * sizeof(unsigned long long), st);
-    if (rc == DCN_OK) rc = dcn::fill_bytes_async(closer, 0, R * 2 * sizeof(int32_t), st);
-    if (rc == DCN_OK) rc = dcn::fill_bytes_async(a.dist_sum, 0, R * 2 * sizeof(unsigned long long), st);
-    if (rc == DCN_OK) rc = dcn::fill_bytes_async(a.gt_d, 0, align256(R * sizeof(float)), st);
-    if (rc == DCN_OK) rc = dcn::fill_bytes_async(mask_pixels, 0, (size_t)p * sizeof(int32_t), st);
-    if (rc == DCN_OK) rc = dcn::fill_bytes_async(status, 0, sizeof(int32_t), st);
-    if (rc == DCN_OK) rc = dcn::fill_bytes_async(flag, 0, sizeof(int32_t), st);
+    int32_t* flag;
+    const int rc = dcn::prepare_stats_scratch(workspace, max_rows, closer, mask_pixels, p, status, offsets, st, a.best,
+                                              a.dist_sum, a.gt_d, flag);
     if (rc != DCN_OK) return rc;
-    hipLaunchKernelGGL(check_offsets_kernel, dim3(dcn::ceil_div(p, 256)), dim3(256), 0, st, offsets, p, max_rows, flag, status);
+    a.count = closer;
+    a.offsets_bad = flag;
     a.res_a = res_a;
     a.res_b = res_b;
     a.mask_b = mask_b;
@@ -211,16 +193,7 @@ extern "C" int dcn_match_statistics_pairs(int p, int h, int w, int d, const floa
     a.d = d;
     a.max_pair_rows = max_pair_rows;
     const dim3 grid((unsigned)dcn::ceil_div64(hw, kMT), (unsigned)p), block(kMT);
-#define DCN_PS(DT) hipLaunchKernelGGL((pair_stats_kernel<DT>), grid, block, 0, st, a)
-    switch (d) {
-        case 3: DCN_PS(3); break;
-        case 4: DCN_PS(4); break;
-        case 8: DCN_PS(8); break;
-        case 16: DCN_PS(16); break;
-        case 32: DCN_PS(32); break;
-        default: DCN_PS(0); break;
-    }
-#undef DCN_PS
+    DCN_LAUNCH_FOR_D(d, pair_stats_kernel, grid, block, st, a);
     PairRows b;
     b.depth_a = depth_a;
     b.depth_b = depth_b;

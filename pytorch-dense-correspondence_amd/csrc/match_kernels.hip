@@ -213,17 +213,7 @@ extern "C" int dcn_match_statistics(const float* res, int64_t hw, int w, int d, 
     if (dcn::fill_bytes_async(count, 0, (size_t)q * 2 * sizeof(int32_t), st) != DCN_OK) return DCN_E_LAUNCH;
     if (dcn::fill_bytes_async(dist_sum, 0, (size_t)q * 2 * sizeof(float), st) != DCN_OK) return DCN_E_LAUNCH;
     const dim3 grid((unsigned)dcn::ceil_div64(hw, kMT)), block(kMT);
-#define DCN_MS(DT) \
-    hipLaunchKernelGGL((match_stats_kernel<DT>), grid, block, 0, st, res, hw, w, d, queries, gt_idx, q, mask, o)
-    switch (d) {
-        case 3: DCN_MS(3); break;
-        case 4: DCN_MS(4); break;
-        case 8: DCN_MS(8); break;
-        case 16: DCN_MS(16); break;
-        case 32: DCN_MS(32); break;
-        default: DCN_MS(0); break;
-    }
-#undef DCN_MS
+    DCN_LAUNCH_FOR_D(d, match_stats_kernel, grid, block, st, res, hw, w, d, queries, gt_idx, q, mask, o);
     hipLaunchKernelGGL(match_stats_unpack_kernel, dim3(dcn::ceil_div(2 * q, 256)), dim3(256), 0, st,
                        (const unsigned long long*)o.best, q, mask ? 1 : 0, best_idx, best_dist, count, dist_sum);
     return dcn::check_launch();
@@ -241,17 +231,7 @@ extern "C" int dcn_find_best_match(const float* res, int64_t hw, int d, const fl
     unsigned long long* best = (unsigned long long*)workspace;
     if (dcn::fill_bytes_async(best, 0xFF, (size_t)q * sizeof(unsigned long long), st) != DCN_OK) return DCN_E_LAUNCH;
     const dim3 grid((unsigned)dcn::ceil_div64(hw, kMT)), block(kMT);
-#define DCN_BM(DT) \
-    hipLaunchKernelGGL((best_match_kernel<DT>), grid, block, 0, st, res, hw, d, queries, q, mask, best, norm_diffs)
-    switch (d) {
-        case 3: DCN_BM(3); break;
-        case 4: DCN_BM(4); break;
-        case 8: DCN_BM(8); break;
-        case 16: DCN_BM(16); break;
-        case 32: DCN_BM(32); break;
-        default: DCN_BM(0); break;
-    }
-#undef DCN_BM
+    DCN_LAUNCH_FOR_D(d, best_match_kernel, grid, block, st, res, hw, d, queries, q, mask, best, norm_diffs);
     hipLaunchKernelGGL(best_match_unpack_kernel, dim3(dcn::ceil_div(q, 256)), dim3(256), 0, st,
                        (const unsigned long long*)best, q, best_idx, best_dist);
     return dcn::check_launch();

@@ -382,7 +382,7 @@ inline int prune_parts(int n, int64_t count_a, int64_t count_b) {
     return (int)(parts < 1 ? 1 : (parts > kPruneMaxParts ? kPruneMaxParts : parts));
 }
 
-inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
+using dcn::align256;
 
 }  // namespace
 

@@ -462,7 +462,7 @@ __global__ void __launch_bounds__(kThreads) write_kernel(OutArgs a) {
     if (bad) atomicOr(a.status, bad);
 }
 
-inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
+using dcn::align256;
 
 struct Workspace {
     int32_t *lists, *seg, *pix;

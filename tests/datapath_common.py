@@ -1,5 +1,5 @@
 """Shared by tests/test_emu_datapath.py (host emulation, "cpu") and tests/test_gpu_datapath.py (gfx950, "cuda"); not a test
-module.  The host side of the device data path (dcn_hip/samples.py, frames.py, evaluate.py, merge.py, augment.py, pairgen.py and
+module.  The host side of the device data path (dcn_hip/samples.py, frames.py, evaluate/, merge.py, augment.py, pairgen.py and
 the host half of csrc/sample_kernels.hip):
 
   a. every clause of the argument tests of the five sample entry points, one argument at a time on otherwise valid calls (n = 1,

@@ -1,5 +1,5 @@
 """Shared by tests/test_emu_descstats.py and tests/test_gpu_descstats.py: the checks of the descriptor statistics
-(csrc/descstats_kernels.hip, dcn_hip/evaluate.py) against the descstats goldens (the reference's own
+(csrc/descstats_kernels.hip, dcn_hip/evaluate/descstats.py) against the descstats goldens (the reference's own
 compute_descriptor_statistics / update_stats loop on prepared descriptor images, tests/golden/
 make_descstats_goldens_from_reference.py), a float64 numpy statement and a float32 numpy replay of the combine stage.
 

@@ -1,4 +1,4 @@
-"""Pins the across-object evaluation (csrc/acrossobj_kernels.hip, dcn_hip/evaluate.py): executes the REFERENCE's own functions
+"""Pins the across-object evaluation (csrc/acrossobj_kernels.hip, dcn_hip/evaluate/across_objects.py): executes the REFERENCE's own functions
 -- read from the reference tree at run time through tests/reference_py3.py, never copied --
   correspondence_finder.random_sample_from_masked_image (correspondence_finder.py:68-90), with ``random.sample`` wrapped so
   that its ``rand_inds`` are recorded

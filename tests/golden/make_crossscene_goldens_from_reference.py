@@ -1,4 +1,4 @@
-"""Pins the cross-scene evaluation (csrc/crossscene_kernels.hip, dcn_hip/evaluate.py): executes the REFERENCE's own source
+"""Pins the cross-scene evaluation (csrc/crossscene_kernels.hip, dcn_hip/evaluate/cross_scene.py): executes the REFERENCE's own source
 text -- read from /root/reference at run time, never copied --
   dense_correspondence/evaluation/evaluation.py single_cross_scene_image_pair_quantitative_analysis (:610-781; the Python-2
   text converted in memory by lib2to3, as tests/reference_py3.py converts modules)

@@ -1,4 +1,4 @@
-"""Pins the evaluation curves (dcn_hip/evaluate.py: cumulative_frequencies, evaluation_curves, curves_to_host,
+"""Pins the evaluation curves (dcn_hip/evaluate/curves.py: cumulative_frequencies, evaluation_curves, curves_to_host,
 area_above_curve; csrc/curve_kernels.hip): executes the REFERENCE's own source text -- read from the reference tree at run
 time, never copied --
   dense_correspondence/evaluation/evaluation.py DenseCorrespondenceEvaluationPlotter.make_cdf_plot (:2658-2674) and

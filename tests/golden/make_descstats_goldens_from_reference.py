@@ -1,4 +1,4 @@
-"""Pins the descriptor statistics (csrc/descstats_kernels.hip, dcn_hip/evaluate.py): executes the REFERENCE's own source lines
+"""Pins the descriptor statistics (csrc/descstats_kernels.hip, dcn_hip/evaluate/descstats.py): executes the REFERENCE's own source lines
 -- read from /root/reference at run time, never copied --
   dense_correspondence/evaluation/evaluation.py:2177-2292   (the inner functions of compute_descriptor_statistics_on_dataset,
   compute_descriptor_statistics / update_stats, its loop over the images and the final scaling)

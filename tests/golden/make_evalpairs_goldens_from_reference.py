@@ -1,5 +1,5 @@
 """Pins the batched evaluation (csrc/evaluate_kernels.hip, the matches-only entry of csrc/sample_kernels.hip,
-dcn_hip/evaluate.py): executes the REFERENCE's own source lines -- read from /root/reference at run time, never copied --
+dcn_hip/evaluate/pairs.py): executes the REFERENCE's own source lines -- read from /root/reference at run time, never copied --
   dense_correspondence/evaluation/evaluation.py:1045-1175   (the body of compute_descriptor_match_statistics)
   evaluation.py clip_pixel_to_image_size_and_round (:604-607), is_depth_valid (:961-972), compute_3d_position (:1181-1200)
   evaluation.py:37-64 DCNEvaluationPandaTemplate on evaluation/utils.py's PandaDataFrameWrapper (a recording stub when pandas

@@ -1,4 +1,4 @@
-"""Pins the class-consistent keypoint evaluation (dcn_hip/evaluate.py: keypoint_labels, keypoint_rows, evaluate_keypoint_rows,
+"""Pins the class-consistent keypoint evaluation (dcn_hip/evaluate/keypoints.py: keypoint_labels, keypoint_rows, evaluate_keypoint_rows,
 keypoint_table; csrc/crossscene_kernels.hip's wide statistics kernel): executes the REFERENCE's own source text -- read from
 /root/reference at run time, never copied --
   dense_correspondence/evaluation/evaluation.py single_image_pair_cross_scene_keypoints_quantitative_analysis (:1433-1552; the

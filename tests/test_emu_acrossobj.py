@@ -1,4 +1,4 @@
-"""Across-object evaluation (csrc/acrossobj_kernels.hip, dcn_hip/evaluate.py) through the host-emulation build: the reference's
+"""Across-object evaluation (csrc/acrossobj_kernels.hip, dcn_hip/evaluate/across_objects.py) through the host-emulation build: the reference's
 own mask sampling and best-match search replayed (acrossobj goldens), the seeded sampling, the device-side status bits, ragged
 batches, the host-side ValueErrors, the pair choice and evaluate_network_across_objects on a small store."""
 import subprocess

@@ -1,4 +1,4 @@
-"""Cross-scene evaluation (csrc/crossscene_kernels.hip, dcn_hip/evaluate.py) through the host-emulation build: the reference's
+"""Cross-scene evaluation (csrc/crossscene_kernels.hip, dcn_hip/evaluate/cross_scene.py) through the host-emulation build: the reference's
 own per-pair analysis replayed (crossscene goldens), the grouped statistics against the pair-wise entry bit for bit, the
 reprojection against the match search, the device-side status bits, the label and view rules on the host and
 evaluate_network_cross_scene on a small store."""

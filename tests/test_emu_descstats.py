@@ -1,4 +1,4 @@
-"""Descriptor statistics of a dataset (csrc/descstats_kernels.hip, dcn_hip/evaluate.py) through the host-emulation build: the
+"""Descriptor statistics of a dataset (csrc/descstats_kernels.hip, dcn_hip/evaluate/descstats.py) through the host-emulation build: the
 reference's own compute_descriptor_statistics / update_stats loop replayed (descstats goldens), every channel-count path
 with several workgroups per image against a float64 numpy statement, NaN, the argument errors, the frame choice, and the whole
 compute_descriptor_statistics_on_dataset call on a small store with a tiny network (16 x 24 images: the emulated forwards

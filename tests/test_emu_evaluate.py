@@ -1,5 +1,5 @@
 """Evaluation on frame-store image pairs (csrc/evaluate_kernels.hip, dcn_eval_matches of csrc/sample_kernels.hip,
-dcn_hip/evaluate.py) through the host-emulation build: the reference's own match search, subsample and
+dcn_hip/evaluate/pairs.py) through the host-emulation build: the reference's own match search, subsample and
 compute_descriptor_match_statistics replayed (evalpairs goldens), the batched kernel against the per-pair one, the pair choice,
 evaluate_network on a small store with a tiny network, and the host-side ValueErrors."""
 import collections

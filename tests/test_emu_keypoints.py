@@ -1,4 +1,4 @@
-"""Class-consistent keypoint evaluation (dcn_hip/evaluate.py, the wide statistics kernel of csrc/crossscene_kernels.hip) through
+"""Class-consistent keypoint evaluation (dcn_hip/evaluate/keypoints.py, the wide statistics kernel of csrc/crossscene_kernels.hip) through
 the host-emulation build: the reference's own per-pair analysis replayed (keypoints goldens), the wide entry against the
 grouped one bit for bit, a planted tie across strips, the host rules, the device-side status bits,
 evaluate_network_cross_instance and the csv file."""

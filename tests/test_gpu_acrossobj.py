@@ -1,4 +1,4 @@
-"""Across-object evaluation on the MI355X (csrc/acrossobj_kernels.hip, dcn_hip/evaluate.py): the reference goldens on the device,
+"""Across-object evaluation on the MI355X (csrc/acrossobj_kernels.hip, dcn_hip/evaluate/across_objects.py): the reference goldens on the device,
 the chain on a frame store against the single-image best-match kernel called pair by pair, and run-to-run bit identity."""
 import numpy as np
 import pytest

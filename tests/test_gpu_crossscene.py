@@ -1,4 +1,4 @@
-"""Cross-scene evaluation on the MI355X (csrc/crossscene_kernels.hip, dcn_hip/evaluate.py): the reference goldens on the device,
+"""Cross-scene evaluation on the MI355X (csrc/crossscene_kernels.hip, dcn_hip/evaluate/cross_scene.py): the reference goldens on the device,
 the chain against the pair-wise statistics kernels called row by row on the same descriptors, the grouped entry against the
 pair-wise one, and run-to-run bit identity with a planted exact tie."""
 import numpy as np

@@ -1,4 +1,4 @@
-"""Descriptor statistics of a dataset (csrc/descstats_kernels.hip, dcn_hip/evaluate.py) on the MI355X: the checks of
+"""Descriptor statistics of a dataset (csrc/descstats_kernels.hip, dcn_hip/evaluate/descstats.py) on the MI355X: the checks of
 tests/descstats_common.py -- the descstats goldens (the reference's own per-image statistics and update_stats loop), every
 channel-count path at 240 x 320 against a float64 numpy statement with two bit-identical runs, NaN, the argument errors
 (CPU tensors included), the frame choice, and the whole compute_descriptor_statistics_on_dataset call with the real Resnet34_8s

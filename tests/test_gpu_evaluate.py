@@ -1,4 +1,4 @@
-"""Evaluation on frame-store image pairs (csrc/evaluate_kernels.hip, dcn_hip/evaluate.py) on the MI355X: the evalpairs goldens
+"""Evaluation on frame-store image pairs (csrc/evaluate_kernels.hip, dcn_hip/evaluate/pairs.py) on the MI355X: the evalpairs goldens
 (the reference's own match search, subsample and statistics), and one full-size case -- 480 x 640, D = 3, 8 pairs of a synthetic
 store -- for the batched kernel against the per-pair kernel plus a float64 numpy restatement of the 3D half, and for
 evaluate_frame_pairs with the real backbone against the same pipeline run pair by pair.  Reads tests/golden only."""

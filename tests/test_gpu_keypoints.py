@@ -1,4 +1,4 @@
-"""Class-consistent keypoint evaluation on the MI355X (dcn_hip/evaluate.py, the wide statistics kernel of
+"""Class-consistent keypoint evaluation on the MI355X (dcn_hip/evaluate/keypoints.py, the wide statistics kernel of
 csrc/crossscene_kernels.hip): the reference goldens through the chain with the wide entry, the grouped entry and the two-sweep
 path, the wide entry against the grouped one bit for bit, and run-to-run bit identity with a tie planted across strips."""
 import numpy as np

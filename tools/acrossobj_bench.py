@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Times the across-object search (csrc/acrossobj_kernels.hip, dcn_hip/evaluate.py) for 25 pairs x 100 queries of 640 x 480
+"""Times the across-object search (csrc/acrossobj_kernels.hip, dcn_hip/evaluate/across_objects.py) for 25 pairs x 100 queries of 640 x 480
 descriptor images at D = 3 and D = 16, on random masks and descriptors:
 
   1. the whole call: ``evaluate.across_object_queries`` + ``evaluate.best_match_pairs`` (device time between two events);

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Times the cross-scene evaluation (csrc/crossscene_kernels.hip, dcn_hip/evaluate.py) for 5 annotated pairs x 8 labels x
+"""Times the cross-scene evaluation (csrc/crossscene_kernels.hip, dcn_hip/evaluate/cross_scene.py) for 5 annotated pairs x 8 labels x
 (10 + 10) views of 640 x 480 at D = 3 and D = 16, on a synthetic frame store (ten scenes of twelve frames, the cameras turned
 about the point the labelled image's central pixel sees, a pointwise stand-in network):
 
@@ -124,13 +124,14 @@ def run(a, dev, _lib, evaluate):
     for D in a.dims:
         net = PointwiseNetwork(D, dev)
         calls = {"groups": [], "reproject": []}
-        real = evaluate.match_statistics_groups, evaluate.reproject_pixels
-        evaluate.match_statistics_groups = lambda *x, **k: (calls["groups"].append((x, k)), real[0](*x, **k))[1]
-        evaluate.reproject_pixels = lambda *x, **k: (calls["reproject"].append((x, k)), real[1](*x, **k))[1]
+        chain = evaluate.cross_scene                           # (the module whose globals the chain looks the two up in)
+        real = chain.match_statistics_groups, chain.reproject_pixels
+        chain.match_statistics_groups = lambda *x, **k: (calls["groups"].append((x, k)), real[0](*x, **k))[1]
+        chain.reproject_pixels = lambda *x, **k: (calls["reproject"].append((x, k)), real[1](*x, **k))[1]
         try:
             t = evaluate.evaluate_cross_scene_rows(net, store, labels, views)
         finally:
-            evaluate.match_statistics_groups, evaluate.reproject_pixels = real
+            chain.match_statistics_groups, chain.reproject_pixels = real
         assert int(t.status.cpu()[0]) == 0
         rows = torch.nonzero(t.row_pair >= 0)[:, 0]
         n = int(rows.numel())

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Times the descriptor statistics of a dataset (csrc/descstats_kernels.hip, dcn_hip/evaluate.py) at 640 x 480:
+"""Times the descriptor statistics of a dataset (csrc/descstats_kernels.hip, dcn_hip/evaluate/descstats.py) at 640 x 480:
 
   1. the whole ``evaluate.compute_descriptor_statistics_on_dataset`` call for 100 frames of a synthetic store (4 scenes x 60
      frames), D = 3, real Resnet34_8s, 16 images per forward (wall clock around the call, which ends in its one copy to the

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Times the evaluation on frame-store image pairs (csrc/evaluate_kernels.hip, dcn_hip/evaluate.py) for 25 and 100 image pairs
+"""Times the evaluation on frame-store image pairs (csrc/evaluate_kernels.hip, dcn_hip/evaluate/pairs.py) for 25 and 100 image pairs
 of 640 x 480, D = 3, on a synthetic store (4 scenes x 60 frames), real Resnet34_8s:
 
   1. the whole ``evaluate.evaluate_network`` call (wall clock around the call, which ends in its one copy to the host);

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Times the class-consistent keypoint table (dcn_hip/evaluate.py, the wide statistics kernel of csrc/crossscene_kernels.hip)
+"""Times the class-consistent keypoint table (dcn_hip/evaluate/keypoints.py, the wide statistics kernel of csrc/crossscene_kernels.hip)
 at 640 x 480, D = 3 and D = 16, for K = 8, 24 and 64 labelled images x 8 keypoints: every labelled image is searched by
 (K - 1) * 8 = 56, 184 and 504 rows.
 
