@@ -505,14 +505,11 @@ __device__ __forceinline__ void gemm_segment_f16(const GemmConv& p, _Float16* ld
                                                                        acc[tm][tn][4 * q + 2], acc[tm][tn][4 * q + 3]);
         }
         if constexpr (!(WR == 2 && WC == 2 && TM == 2 && TN == 2)) if (inl) {
-            // Completed inside the launch.  The parked partials travel between workgroups on different XCDs (separate
-            // L2s), so they are written and read with device-coherent accesses (sc1: write-through / L2-bypassing) and ordered
-            // against the arrival word by counter waits only -- NO device-scope fence: a release / acquire fence writes back
-            // and invalidates the whole L2 of the XCD under the 31 other CUs that are in the middle of their K loops
-            // (measured: +50 us per launch, profiles/r2b_ab_fence_variant.txt).
+            // Completed inside the launch: the park-and-complete protocol of conv_shared.h (wait, arrival, hand-off and reset are
+            // its sk_arrive / sk_release); what is this kernel's own is how the 32 x 32 accumulators map to 16-byte pieces.
             __shared__ int s_last;
             const __amdgpu_buffer_rsrc_t rs_p = __builtin_amdgcn_make_buffer_rsrc(p.sk_partial, 0, (int)p.sk_bytes, 0x00020000);
-            constexpr int kSc1 = 16;                           // cache-policy bit of buffer loads / stores: device scope
+            constexpr int kSc1 = kSkDeviceScope;
             const int lane_off = (wv * (TM * TN * 16 * 64) + lane * 4) * 4;
             {
                 const int so = (int)((slot - p.sk_partial) * 4);
@@ -531,11 +528,7 @@ __device__ __forceinline__ void gemm_segment_f16(const GemmConv& p, _Float16* ld
             const int rel = tile - p.sk_dp;                    // (index among the stream-K'd tiles)
             const int ua = rel * nk, ub = ua + nk - 1;         // its unit range relative to the start of the stream-K pass
             const int ga = ua / p.sk_units, gb = ub / p.sk_units;
-            __builtin_amdgcn_s_waitcnt(0x0F70);                // vmcnt(0): this work-item's partial has been written through
-            __syncthreads();
-            if (tid == 0) s_last = sk_arrive_is_last(p.sk_count + rel, p.sk_id, gb - ga + 1) ? 1 : 0;
-            __syncthreads();
-            if (s_last) {
+            if (sk_arrive(&s_last, p.sk_count, rel, p.sk_id, gb - ga + 1)) {
 #pragma unroll
                 for (int tm = 0; tm < TM; ++tm)
 #pragma unroll
@@ -567,7 +560,7 @@ __device__ __forceinline__ void gemm_segment_f16(const GemmConv& p, _Float16* ld
                     }
                 }
                 gemm_epilogue<WR, TM, TN, 16, WC>(p, acc, mt, nt, reinterpret_cast<float*>(lds));
-                if (tid == 0) atomicExch(p.sk_count + rel, 0ull);
+                sk_release(p.sk_count + rel);
             }
         }
     }

@@ -8,6 +8,7 @@
 // VGPR staging and no LDS store: tiles are filled by LDS-DMA (`buffer_load_dwordx4 ... lds`, 64 lanes x 16 B land at
 // M0 + 16 lane; rows outside the image / past M carry an out-of-range offset and arrive as zeros) into a lane-linear image
 // whose 16-byte slots are XOR-swizzled on the SOURCE side (slot ^ ((row >> 1) & 7): conflict-free ds_read_b128 fragments).
+// The addressing of a piece, the K traversal and the MFMA burst are shared with the small-tile kernels: see conv_hl32.h.
 //
 // Tile 256 x 256 on 8 wavefronts (2 x 4; wavefront tile 128 x 64 = 8 accumulators of 32 x 32), 32-K stages of 64 KB, two
 // stage buffers.  Schedule (tools/hl_gemm_probe2.hip, profiles/r3a_hl_gemm_probe2.txt): the wavefronts of group 1 (waves
@@ -56,30 +57,21 @@
 #include <atomic>
 #include <type_traits>
 
+#include "conv_hl32.h"
 #include "conv_hlx.h"
-#include "conv_shared.h"
 #include "dcn_tuning.h"
-#include "f16_split.h"
 
 namespace {
 
 using namespace dcnconv;
 using namespace dcnsplit;
 
-typedef __attribute__((address_space(3))) void* hl_lds_ptr;
-
-constexpr int kOob = (int)0x80000000;   // voffset that fails the bounds check of any buffer <= 2 GiB: LDS receives zeros
 constexpr int kHlStage = 65536;         // bytes per 32-K stage: [A rows 0..255][B rows 0..255] x 128 B
 // per tile height: bytes of the A part of a stage (B follows it: 256 rows x 128 B) and of the whole stage
 template <int MT> struct HlStage {
     static constexpr int kA = MT == 5 ? 320 * 128 : 32768, kStage = kA + 32768;
 };
 constexpr int HLK = 32;
-
-// (a NON-template function: inside a template this builtin breaks the host-side kernel stub with this compiler)
-__device__ __forceinline__ void glds16(__amdgpu_buffer_rsrc_t rs, void* lds_dst, int voffset, int soffset) {
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (hl_lds_ptr)lds_dst, 16, voffset, soffset, 0, 0);
-}
 
 // fp32 [rows][C] (C % 32 == 0) -> hl32 [rows][C / 32][hi x32 | lo x32], scaled by pow2_scale(*absmax).
 // One work-item per 8 channels: 32 B in, 16 B of the hi half-line + 16 B of the lo half-line out.
@@ -123,103 +115,46 @@ __device__ __forceinline__ void gemm_segment_hl(const GemmConv& p, unsigned char
     const int cs4 = p.cs * 4;              // bytes per pixel of the activation image
     // A piece a of this wavefront: MT = 4: (i, e) = (a >> 1, a & 1) as above; MT = 3: block i = a, rows 96 g + 32 a + 8 wn + [0, 8)
     auto a_piece_row = [&](int a) { return MT == 4 ? grp * 128 + (a >> 1) * 64 + (2 * wn + (a & 1)) * 8 : grp * GR + a * 32 + wn * 8; };
-    int by[NA], bx[NA], rowoff[NA], voa[NA], vob[2][2];
-    // MT = 5 (160 accumulator registers): instead of the position (by, bx) and the current offset (voa) of every piece, ONE
-    // word per piece with a validity bit per filter tap (taps <= 32: hl_shape) -- the offset of a piece is formed when it is
-    // issued: rowoff +- the tap's (wave-uniform) displacement, or the out-of-range offset.  10 registers instead of 20.
-    unsigned vmask[NA];
-    int cur_delta = 0, cur_bit = 0;
+    // MT = 3 / 4: the current offset (voa) of every piece, recomputed from its position when the filter tap changes.
+    // MT = 5 (160 accumulator registers): instead of the position (by, bx) and voa of every piece, ONE word per piece with a
+    // validity bit per filter tap (taps <= 32: hl_shape) -- the offset of a piece is formed when it is issued: rowoff +- the
+    // tap's (wave-uniform) displacement, or the out-of-range offset.  10 registers instead of 20.
+    Hl32Piece pa[NA];
+    int voa[NA], vob[2][2];
 #pragma unroll
-    for (int a = 0; a < NA; ++a) {
-        const int row = a_piece_row(a) + l8;
-        const int sl = ls ^ ((row >> 1) & 7);
-        const int m = m0 + row;
-        const bool ok = m < p.M;
-        const int mm = ok ? m : 0;
-        const int img = fdiv(mm, p.div_hw), rem = mm - img * p.div_hw.d;
-        const int y = fdiv(rem, p.div_w), x = rem - y * p.div_w.d;
-        by[a] = ok ? (TR ? y + p.pad : y - p.pad) : -(1 << 28);   // (stride 1; rows past M: never inside the image)
-        bx[a] = TR ? x + p.pad : x - p.pad;
-        rowoff[a] = ok ? (img * p.hs * p.ws + by[a] * p.ws + bx[a]) * cs4 + sl * 16 : 0;
-        vmask[a] = 0u;
-        if constexpr (MT == 5) {
-            const int ntap = p.kh * p.kw;
-            for (int tap = 0; tap < ntap; ++tap) {
-                const int r = fdiv(tap, p.div_kw), s = tap - r * p.kw;
-                const int dy = r * p.dil, dx = s * p.dil;
-                bool v;
-                if (TR) {
-                    const int ny = by[a] - dy, nx = bx[a] - dx;
-                    v = ((ny | nx) >= 0) & (ny < p.hs) & (nx < p.ws);
-                } else {
-                    v = ((unsigned)(by[a] + dy) < (unsigned)p.hs) & ((unsigned)(bx[a] + dx) < (unsigned)p.ws);
-                }
-                vmask[a] |= (v ? 1u : 0u) << tap;
-            }
-        }
-    }
+    for (int a = 0; a < NA; ++a) hl32_piece<TR, MT == 5>(p, cs4, m0, a_piece_row(a) + l8, ls, pa[a]);
 #pragma unroll
     for (int j = 0; j < 2; ++j)
 #pragma unroll
         for (int e = 0; e < 2; ++e) {
             const int row = (wv >> 1) * 64 + j * 32 + (2 * (wv & 1) + e) * 8 + l8;
-            const int sl = ls ^ ((row >> 1) & 7);
-            const int n = n0 + row;
-            vob[j][e] = n < p.cd ? n * (nk * 128) + sl * 16 : kOob;
+            vob[j][e] = hl32_vob(p, n0 + row, row, ls, nk);
         }
-    // K traversal: channel-chunk groups outermost (kcg chunks = up to 128 channels), then the filter taps, then the chunks
-    // of the group: the same input pixels come back for the next tap after kcg stages, while they are still in this XCD's L2
-    const int cpt = p.cs / HLK;
-    const int kcg = (cpt & 3) == 0 ? 4 : ((cpt & 1) == 0 ? 2 : 1);
-    const int taps = p.kh * p.kw;
-    int u_grp, u_tap, u_c, u_kt = k0;      // the stage whose LDS-DMA is issued next
-    auto set_tap = [&](int tap) {
-        const int r = fdiv(tap, p.div_kw), s = tap - r * p.kw;
-        const int dy = r * p.dil, dx = s * p.dil;
-        const int delta = (dy * p.ws + dx) * cs4;
-        if constexpr (MT == 5) {
-            cur_delta = TR ? -delta : delta;
-            cur_bit = tap;
-            return;
-        }
+    // K traversal (conv_hl32.h)
+    int u_kt = k0;                         // the stage whose LDS-DMA is issued next
+    Hl32KWalk<TR> kw;
+    auto set_voa = [&](int dy, int dx) {   // (MT = 3 / 4) on a new filter tap
+        if constexpr (MT != 5) {
 #pragma unroll
-        for (int a = 0; a < NA; ++a) {
-            bool ok;
-            if (TR) {
-                const int ny = by[a] - dy, nx = bx[a] - dx;
-                ok = ((ny | nx) >= 0) & (ny < p.hs) & (nx < p.ws);
-            } else {
-                ok = ((unsigned)(by[a] + dy) < (unsigned)p.hs) & ((unsigned)(bx[a] + dx) < (unsigned)p.ws);
-            }
-            voa[a] = ok ? (TR ? rowoff[a] - delta : rowoff[a] + delta) : kOob;
+            for (int a = 0; a < NA; ++a)
+                voa[a] = hl32_tap_inside<TR>(p, pa[a].by, pa[a].bx, dy, dx) ? pa[a].rowoff + kw.delta : kOob;
         }
     };
-    {
-        const int per_grp = taps * kcg;
-        u_grp = k0 / per_grp;
-        const int rem = k0 - u_grp * per_grp;
-        u_tap = rem / kcg;
-        u_c = rem - u_tap * kcg;
-        set_tap(u_tap);
-    }
+    kw.start(p, cs4, k0, set_voa);
     auto advance = [&]() {                 // steps to the next stage of the segment (stays on the last one)
         if (u_kt + 1 < k1) {
             ++u_kt;
-            if (++u_c == kcg) {
-                u_c = 0;
-                if (++u_tap == taps) { u_tap = 0; ++u_grp; }
-                set_tap(u_tap);
-            }
+            kw.advance(p, 1, set_voa);
         }
     };
     // pieces of the stage the traversal state points at, into stage buffer `buf`
     auto issue_a = [&](int buf, int a) {
-        const int vo = MT == 5 ? (((vmask[a] >> cur_bit) & 1u) ? rowoff[a] + cur_delta : kOob) : voa[a];
-        glds16(rs_a, lds + buf * kHlStage + a_piece_row(a) * 128, vo, (u_grp * kcg + u_c) * 128);
+        const int vo = MT == 5 ? kw.voffset_a(pa[a]) : voa[a];
+        glds16(rs_a, lds + buf * kHlStage + a_piece_row(a) * 128, vo, kw.soffset_a());
     };
     auto issue_b = [&](int buf, int j) {
         unsigned char* d = lds + buf * kHlStage + kAB + ((wv >> 1) * 64 + j * 32 + 2 * (wv & 1) * 8) * 128;
-        const int soff = (u_tap * cpt + u_grp * kcg + u_c) * 128;
+        const int soff = kw.soffset_b();
         glds16(rs_b, d, vob[j][0], soff);
         glds16(rs_b, d + 1024, vob[j][1], soff);
     };
@@ -240,10 +175,9 @@ __device__ __forceinline__ void gemm_segment_hl(const GemmConv& p, unsigned char
     // fq = lane >> 4) holds k-octet fq of the stage's 32 k of row fr of a 16-row block; plane 0 = hi, 1 = lo.  The source-side
     // XOR swizzle (slot ^ ((row >> 1) & 7)) is conflict-free for the ds_read_b128 lane groups of this layout too (rows 0-3 /
     // 12-15 of one octet with rows 4-11 of the next: 16 distinct (row parity, slot) pairs).
-    const int fr = lane & 15, fq = lane >> 4, swz = (fr >> 1) & 7;
     int foff[2];   // [plane]: byte offset of the lane's slot inside its 16-row block
 #pragma unroll
-    for (int pl = 0; pl < 2; ++pl) foff[pl] = fr * 128 + ((pl * 4 + fq) ^ swz) * 16;
+    for (int pl = 0; pl < 2; ++pl) foff[pl] = hl32_foff(lane, pl);
     const int a_row = (grp * GR) * 128, b_row = kAB + (wn * 64) * 128;
 
     f32x4_t acc[2 * MT][4];   // [row block of 16][column block of 16]: rows GR g + 16 tb, columns 64 wn + 16 cb
@@ -253,8 +187,7 @@ __device__ __forceinline__ void gemm_segment_hl(const GemmConv& p, unsigned char
         for (int j = 0; j < 4; ++j) acc[i][j] = f32x4_t{0.f, 0.f, 0.f, 0.f};
     using T = std::true_type;
     using F = std::false_type;
-    // raw s_barrier: no fence, LDS-DMA stays in flight across it
-    auto bar = [&]() { __builtin_amdgcn_sched_barrier(0); __builtin_amdgcn_s_barrier(); __builtin_amdgcn_sched_barrier(0); };
+    auto bar = [&]() { raw_barrier(); };
   if constexpr (MT == 4) {
     h8 fa[4][2], fb[2][2];   // A: [row block of the quadrant's 64 rows][plane], B: [column block of its 32 columns][plane]
     auto read_a = [&](int buf, int i) {
@@ -274,15 +207,7 @@ __device__ __forceinline__ void gemm_segment_hl(const GemmConv& p, unsigned char
     // product-type outermost, the eight accumulators of the quadrant in between; the small cross terms before hi * hi
     auto mfma_quadrant = [&](int i, int j) {
         if (p.hl_setprio) __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-        for (int pt = 0; pt < 3; ++pt)
-#pragma unroll
-            for (int rb = 0; rb < 4; ++rb)
-#pragma unroll
-                for (int cb = 0; cb < 2; ++cb)
-                    acc[4 * i + rb][2 * j + cb] = __builtin_amdgcn_mfma_f32_16x16x32_f16(pt == 0 ? fa[rb][1] : fa[rb][0],
-                                                                                         pt == 1 ? fb[cb][1] : fb[cb][0],
-                                                                                         acc[4 * i + rb][2 * j + cb], 0, 0, 0);
+        hl32_mfma3<4, 2>(fa, fb, acc, 4 * i, 2 * j);
         if (p.hl_setprio) __builtin_amdgcn_s_setprio(0);
     };
     // one phase of stage s (LDS buffer s & 1).  MORE: stage s + 1 exists -- issue its half-tile p and leave two half-tiles
@@ -347,14 +272,7 @@ __device__ __forceinline__ void gemm_segment_hl(const GemmConv& p, unsigned char
     };
     auto mfma_block = [&](int tm) {
         if (p.hl_setprio) __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-        for (int pt = 0; pt < 3; ++pt)
-#pragma unroll
-            for (int rb = 0; rb < 2; ++rb)
-#pragma unroll
-                for (int cb = 0; cb < 4; ++cb)
-                    acc[2 * tm + rb][cb] = __builtin_amdgcn_mfma_f32_16x16x32_f16(pt == 0 ? fa[rb][1] : fa[rb][0],
-                                                                                  pt == 1 ? fb[cb][1] : fb[cb][0], acc[2 * tm + rb][cb], 0, 0, 0);
+        hl32_mfma3<2, 4>(fa, fb, acc, 2 * tm, 0);
         if (p.hl_setprio) __builtin_amdgcn_s_setprio(0);
     };
     // one phase of stage s (LDS buffer s & 1).  AHEAD: how many later stages of the segment exist (2 = at least two).
@@ -473,57 +391,34 @@ __device__ __forceinline__ void gemm_segment_hl(const GemmConv& p, unsigned char
     bool complete = k0 == 0 && k1 == nk;
     int rel = 0;
     if (!complete) {
-        // ---- stream-K partial: parked device-coherently, completed by the last contributor inside the launch
-        // (conv_f16_kernels.hip, gemm_segment_f16: same protocol; slot layout [wavefront][row block][column block][lane] float4)
-        constexpr int TM = MT;
-        const __amdgpu_buffer_rsrc_t rs_p = __builtin_amdgcn_make_buffer_rsrc(p.sk_partial, 0, (int)p.sk_bytes, 0x00020000);
-        constexpr int kSc1 = 16;
+        // ---- stream-K partial: parked device-coherently, completed by the last contributor inside the launch (the protocol:
+        // conv_shared.h; slot layout [wavefront][row block][column block][lane] float4)
         constexpr int kPieces = 2 * MT * 4;   // float4 pieces per lane
-        const int lane_off = (wv * (kPieces * 64) + lane) * 16;
-        {
-            const int so = (int)((slot - p.sk_partial) * 4);
-#pragma unroll
-            for (int pc = 0; pc < kPieces; ++pc)
-                __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, acc[pc >> 2][pc & 3]), rs_p, lane_off + pc * 1024, so, kSc1);
-        }
+        constexpr int kBatch = MT == 4 ? 16 : (MT == 3 ? 12 : 10);
+        const SkPartials parked{__builtin_amdgcn_make_buffer_rsrc(p.sk_partial, 0, (int)p.sk_bytes, 0x00020000),
+                                (wv * (kPieces * 64) + lane) * 16};
+        parked.park((int)((slot - p.sk_partial) * 4), acc);
         rel = tile - p.sk_dp;
         const int ua = rel * nk, ub = ua + nk - 1;
         const int ga = ua / p.sk_units, gb = ub / p.sk_units;
-        __builtin_amdgcn_s_waitcnt(0x0F70);                // vmcnt(0): this work-item's partial has been written through
-        __syncthreads();
         int* s_last = reinterpret_cast<int*>(lds + 2 * kHlStage - 16);   // (inside the one LDS array: see the header)
-        if (tid == 0) *s_last = sk_arrive_is_last(p.sk_count + rel, p.sk_id, gb - ga + 1) ? 1 : 0;
-        __syncthreads();
-        complete = *s_last != 0;
+        complete = sk_arrive(s_last, p.sk_count, rel, p.sk_id, gb - ga + 1);
         if (complete) {
 #pragma unroll
             for (int tb = 0; tb < 2 * MT; ++tb)
 #pragma unroll
                 for (int cb = 0; cb < 4; ++cb) acc[tb][cb] = f32x4_t{0.f, 0.f, 0.f, 0.f};
-            // (each contributor's partial in batches of loads of 16 B issued back to back, then added: left to itself the
-            // compiler waits for every 4 loads -- device-coherent round trips on the critical path of the launch)
-            constexpr int kBatch = TM == 4 ? 16 : (TM == 3 ? 12 : 10);
-            static_assert(kPieces % kBatch == 0, "whole batches");
             for (int g = ga; g <= gb; ++g) {               // fixed order, own partial included: deterministic
                 const int first_tile = (g * p.sk_units) / nk;
                 const int so = (2 * g + (first_tile == rel ? 0 : 1)) * (BM * 256 * 4);
-#pragma unroll
-                for (int b0 = 0; b0 < kPieces; b0 += kBatch) {
-                    u32x4 t[kBatch];
-#pragma unroll
-                    for (int j = 0; j < kBatch; ++j) t[j] = __builtin_amdgcn_raw_buffer_load_b128(rs_p, lane_off + (b0 + j) * 1024, so, kSc1);
-                    __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-                    for (int j = 0; j < kBatch; ++j) acc[(b0 + j) >> 2][(b0 + j) & 3] += __builtin_bit_cast(f32x4_t, t[j]);
-                    __builtin_amdgcn_sched_barrier(0);
-                }
+                DCN_SK_ADD_PARKED(parked, so, acc, 4, kPieces, kBatch);
             }
             __syncthreads();                               // (s_last has been read by everyone: the epilogue reuses the array)
         }
     }
     if (complete) {
         gemm_epilogue16<2 * MT, 4, BM, 256>(p, acc, mt, nt, grp, grp * GR, wn * 64, reinterpret_cast<float*>(lds));
-        if (!(k0 == 0 && k1 == nk) && tid == 0) atomicExch(p.sk_count + rel, 0ull);
+        if (!(k0 == 0 && k1 == nk)) sk_release(p.sk_count + rel);
     }
 }
 

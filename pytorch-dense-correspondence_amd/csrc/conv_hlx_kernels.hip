@@ -1,5 +1,5 @@
 // Small-tile variants of the pre-split (hl32) LDS-DMA gather-GEMM (conv_hl_kernels.hip has the operand format, the LDS
-// image and the big 256 / 192 / 320-row tiles): forward convolution and dgrad for the launches that do NOT fill the 256 CUs
+// image and the big 256 / 192 / 320-row tiles; the tile primitives both share: see conv_hl32.h): forward convolution and dgrad for the launches that do NOT fill the 256 CUs
 // with 256 x 256 output tiles -- the reference's own operating point (training.yaml:14 `batch_size: 1`, and the two separate
 // forward calls of training.py:329-333: M = 4 800 .. 19 200 rows per launch in layers 3-4), layer 3 at 8 images (38 400 x 256
 // outputs = 150 tiles of 256 rows), and the 128-channel layers.
@@ -15,14 +15,14 @@
 // 38 400 x 256 outputs are 240 tiles of 160 x 256 (layer 3 at 8 images: ONE round on 256 CUs instead of 200 tiles of 192);
 // 9 600 x 512 and 19 200 x 256 are 240 tiles of 160 x 128.  What is smaller still is split along K over `ksplit`
 // workgroups per tile (contiguous ranges of stages; partial tiles parked device-coherently, summed in FIXED order by whichever
-// workgroup arrives last, inside the launch -- the stream-K completion protocol of conv_shared.h): bit-reproducible.
+// workgroup arrives last, inside the launch -- the park-and-complete protocol: see conv_shared.h): bit-reproducible.
 //
 // The loop is the plain double-buffered one (no wavefront-group phase offset): per stage
 //     s_waitcnt vmcnt(0) | s_barrier | LDS-DMA of stage s + 1 into the other buffer | fragment reads + 60 MFMAs of stage s
 // -- the barrier publishes stage s (every wavefront has waited for its own pieces) and retires the reads of stage s - 1 (the
 // buffer stage s + 1 overwrites); the DMA has the whole compute slot of a stage to land.  Two wavefronts per SIMD drift
 // apart and fill each other's waits.  Fragment reads: lane (row l & 15, k-octet l >> 4) reads 16 B of slot
-// (plane * 4 + octet) ^ ((row >> 1) & 7) -- the source-side XOR swizzle of conv_hl_kernels.hip; conflict-free for the
+// (plane * 4 + octet) ^ ((row >> 1) & 7) -- the source-side XOR swizzle (see conv_hl32.h); conflict-free for the
 // ds_read_b128 lane groups of gfx950 as well (rows 0-3 / 12-15 of one octet with rows 4-11 of the next: 16 distinct
 // (row parity, slot) pairs).
 #include <algorithm>
@@ -30,19 +30,17 @@
 #include <type_traits>
 #include <unordered_map>
 
+#include "conv_hl32.h"
 #include "conv_hlx.h"
 #include "dcn_tuning.h"
-#include "f16_split.h"
 
 namespace {
 
 using namespace dcnconv;
 using namespace dcnsplit;
 
-typedef __attribute__((address_space(3))) void* hlx_lds_ptr;
 typedef f32x4_t f32x4;
 
-constexpr int kOob = (int)0x80000000;   // voffset that fails the bounds check of any buffer <= 2 GiB: LDS receives zeros
 constexpr int XR = 160;                 // rows per tile
 constexpr int XTM = 5, XTN = 4;         // 16 x 16 accumulator tiles per wavefront: 80 rows x 64 columns
 
@@ -55,11 +53,6 @@ template <int KG> struct Hlx {
     static constexpr int NB = BN / 64;                    // B row groups (8 lines) per wavefront and chunk
     static constexpr int TNE = XTN / KG;                  // accumulator columns a wavefront owns in the epilogue
 };
-
-// (a NON-template function: inside a template this builtin breaks the host-side kernel stub with this compiler)
-__device__ __forceinline__ void glds16x(__amdgpu_buffer_rsrc_t rs, void* lds_dst, int voffset, int soffset) {
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (hlx_lds_ptr)lds_dst, 16, voffset, soffset, 0, 0);
-}
 
 // TR: dgrad (the gather runs over the output gradient with mirrored taps).
 template <bool TR, int KG>
@@ -90,97 +83,48 @@ conv_gemm_hlx_kernel(GemmConv p) {
     //   B (BN / 8 groups): wv + 8 b, b < NB
     const int l8 = lane >> 3, ls = lane & 7;
     const int cs4 = p.cs * 4;              // bytes per pixel of the activation image
-    const int taps = p.kh * p.kw;
-    int rowoff[3];
-    unsigned vmask[3];                     // one validity bit per filter tap (taps <= 32)
+    Hl32Piece pa[3];                       // (validity of the row under every filter tap as a mask: taps <= 32, hlx_shape)
 #pragma unroll
     for (int a = 0; a < 3; ++a) {
-        const int rg = a < 2 ? wv + 8 * a : 16 + (wv & 3);
-        const int row = rg * 8 + l8;
-        const int sl = ls ^ ((row >> 1) & 7);
-        const int m = m0 + row;
-        const bool ok = m < p.M;
-        const int mm = ok ? m : 0;
-        const int img = fdiv(mm, p.div_hw), rem = mm - img * p.div_hw.d;
-        const int y = fdiv(rem, p.div_w), x = rem - y * p.div_w.d;
-        const int by = TR ? y + p.pad : y - p.pad, bx = TR ? x + p.pad : x - p.pad;   // (stride 1)
-        rowoff[a] = (img * p.hs * p.ws + by * p.ws + bx) * cs4 + sl * 16;
-        unsigned vm = 0u;
-        for (int tap = 0; tap < taps; ++tap) {
-            const int r = fdiv(tap, p.div_kw), s = tap - r * p.kw;
-            const int dy = r * p.dil, dx = s * p.dil;
-            bool v;
-            if (TR) {
-                const int ny = by - dy, nx = bx - dx;
-                v = ((ny | nx) >= 0) & (ny < p.hs) & (nx < p.ws);
-            } else {
-                v = ((unsigned)(by + dy) < (unsigned)p.hs) & ((unsigned)(bx + dx) < (unsigned)p.ws);
-            }
-            vm |= (v ? 1u : 0u) << tap;
-        }
-        vmask[a] = ok ? vm : 0u;
+        const int row = (a < 2 ? wv + 8 * a : 16 + (wv & 3)) * 8 + l8;
+        hl32_piece<TR, true>(p, cs4, m0, row, ls, pa[a]);
     }
     int vob[NB];
 #pragma unroll
     for (int b = 0; b < NB; ++b) {
         const int row = (wv + 8 * b) * 8 + l8;
-        const int sl = ls ^ ((row >> 1) & 7);
-        const int n = n0 + row;
-        vob[b] = n < p.cd ? n * (nk * 128) + sl * 16 : kOob;
+        vob[b] = hl32_vob(p, n0 + row, row, ls, nk);
     }
-    // K traversal (as conv_hl_kernels.hip): channel-chunk groups outermost (kcg chunks), then the filter taps, then the chunks
-    // of the group; a KG = 2 stage is two consecutive chunks of one group and tap (kcg is even: hlx_shape)
-    const int cpt = p.cs / 32;
-    const int kcg = (cpt & 3) == 0 ? 4 : ((cpt & 1) == 0 ? 2 : 1);
-    int u_grp, u_tap, u_c, cur_delta = 0, cur_bit = 0;
-    auto set_tap = [&](int tap) {
-        const int r = fdiv(tap, p.div_kw), s = tap - r * p.kw;
-        const int delta = (r * p.dil * p.ws + s * p.dil) * cs4;
-        cur_delta = TR ? -delta : delta;
-        cur_bit = tap;
-    };
-    {
-        const int k0 = ss0 * KG, per_grp = taps * kcg;
-        u_grp = k0 / per_grp;
-        const int rem = k0 - u_grp * per_grp;
-        u_tap = rem / kcg;
-        u_c = rem - u_tap * kcg;
-        set_tap(u_tap);
-    }
-    auto advance = [&]() {                 // to the next stage (KG chunks on)
-        u_c += KG;
-        if (u_c >= kcg) {
-            u_c = 0;
-            if (++u_tap == taps) { u_tap = 0; ++u_grp; }
-            set_tap(u_tap);
-        }
-    };
-    auto voa = [&](int a) { return ((vmask[a] >> cur_bit) & 1u) ? rowoff[a] + cur_delta : kOob; };
+    // K traversal (conv_hl32.h); a KG = 2 stage is two consecutive chunks of one group and tap (kcg is even: hlx_shape)
+    Hl32KWalk<TR> kw;
+    auto no_tap_work = [](int, int) {};    // (the validity of every tap is in the pieces' masks)
+    kw.start(p, cs4, ss0 * KG, no_tap_work);
+    auto advance = [&]() { kw.advance(p, KG, no_tap_work); };   // to the next stage (KG chunks on)
+    auto voa = [&](int a) { return kw.voffset_a(pa[a]); };
     auto issue = [&](int buf) {            // every piece of the stage the traversal state points at
         unsigned char* st = lds + buf * kStage;
-        const int soa = (u_grp * kcg + u_c) * 128, sob = (u_tap * cpt + u_grp * kcg + u_c) * 128;
+        const int soa = kw.soffset_a(), sob = kw.soffset_b();
 #pragma unroll
         for (int ch = 0; ch < KG; ++ch) {
             unsigned char* cbase = st + ch * kChunk;
-            glds16x(rs_a, cbase + wv * 1024, voa(0), soa + ch * 128);
-            glds16x(rs_a, cbase + (wv + 8) * 1024, voa(1), soa + ch * 128);
+            glds16(rs_a, cbase + wv * 1024, voa(0), soa + ch * 128);
+            glds16(rs_a, cbase + (wv + 8) * 1024, voa(1), soa + ch * 128);
 #pragma unroll
-            for (int b = 0; b < NB; ++b) glds16x(rs_b, cbase + XR * 128 + (wv + 8 * b) * 1024, vob[b], sob + ch * 128);
+            for (int b = 0; b < NB; ++b) glds16(rs_b, cbase + XR * 128 + (wv + 8 * b) * 1024, vob[b], sob + ch * 128);
         }
         if (KG == 1) {
-            if (wv < 4) glds16x(rs_a, st + (16 + wv) * 1024, voa(2), soa);
+            if (wv < 4) glds16(rs_a, st + (16 + wv) * 1024, voa(2), soa);
         } else {
             const int ch = wv >> 2;
-            glds16x(rs_a, st + ch * kChunk + (16 + (wv & 3)) * 1024, voa(2), soa + ch * 128);
+            glds16(rs_a, st + ch * kChunk + (16 + (wv & 3)) * 1024, voa(2), soa + ch * 128);
         }
     };
 
     // ---- fragments: lane (fr = lane & 15, fq = lane >> 4) holds 8 consecutive k (octet fq of the chunk's 32) of row fr of a
     // 16-row tile; plane 0 = hi, 1 = lo
-    const int fr = lane & 15, fq = lane >> 4, swz = (fr >> 1) & 7;
     int foff[2];
 #pragma unroll
-    for (int pl = 0; pl < 2; ++pl) foff[pl] = fr * 128 + ((pl * 4 + fq) ^ swz) * 16;
+    for (int pl = 0; pl < 2; ++pl) foff[pl] = hl32_foff(lane, pl);
     const int a_row = (wm * 80) * 128, b_row = XR * 128 + (wn * 64) * 128;
 
     f32x4 acc[XTM][XTN];
@@ -188,7 +132,7 @@ conv_gemm_hlx_kernel(GemmConv p) {
     for (int i = 0; i < XTM; ++i)
 #pragma unroll
         for (int j = 0; j < XTN; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-    auto bar = [&]() { __builtin_amdgcn_sched_barrier(0); __builtin_amdgcn_s_barrier(); __builtin_amdgcn_sched_barrier(0); };
+    auto bar = [&]() { raw_barrier(); };
     // compute slot of a stage in two parts (rows 0-47 of the wavefront's block with the B fragments, rows 48-79), so that the
     // LDS-DMA issue of the next stage can sit in front of the first part (wavefronts 0-3) or between the parts (wavefronts
     // 4-7): wavefronts w and w + 4 share a SIMD, and with every wavefront released by the same barrier an unstaggered loop
@@ -209,14 +153,8 @@ conv_gemm_hlx_kernel(GemmConv p) {
     // product type outermost (the small cross terms before hi x hi), the part's independent accumulators in between
     auto mm = [&](auto t0, auto t1) {
         __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-        for (int pt = 0; pt < 3; ++pt)
-#pragma unroll
-            for (int tm = decltype(t0)::value; tm < decltype(t1)::value; ++tm)
-#pragma unroll
-                for (int tn = 0; tn < XTN; ++tn)
-                    acc[tm][tn] = __builtin_amdgcn_mfma_f32_16x16x32_f16(pt == 0 ? fa[tm][1] : fa[tm][0],
-                                                                         pt == 1 ? fb[tn][1] : fb[tn][0], acc[tm][tn], 0, 0, 0);
+        constexpr int T0 = decltype(t0)::value, T1 = decltype(t1)::value;
+        hl32_mfma3<T1 - T0, XTN>(fa + T0, fb, acc, T0, 0);
         __builtin_amdgcn_s_setprio(0);
     };
     using I0 = std::integral_constant<int, 0>;
@@ -344,25 +282,12 @@ conv_gemm_hlx_kernel(GemmConv p) {
     if (S > 1) {
         // ---- K split over workgroups: park the partial tile device-coherently ([wavefront][tm][tn][lane] float4 -- 160 x BN
         // floats per (tile, split)), count in; the last arriver sums the S partials in fixed order (its own included)
-        constexpr int kSc1 = 16;
+        // (the protocol: conv_shared.h)
         constexpr int kSlotBytes = XR * BN * 4;
-        const __amdgpu_buffer_rsrc_t rs_p = __builtin_amdgcn_make_buffer_rsrc(p.sk_partial, 0, (int)p.sk_bytes, 0x00020000);
-        const int lane_off = (wv * (XTM * TNE * 64) + lane) * 16;
-        {
-            const int so = (tile * S + split) * kSlotBytes;
-#pragma unroll
-            for (int tm = 0; tm < XTM; ++tm)
-#pragma unroll
-                for (int tn = 0; tn < TNE; ++tn)
-                    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, out[tm][tn]), rs_p,
-                                                           lane_off + (tm * TNE + tn) * 1024, so, kSc1);
-        }
-        __builtin_amdgcn_s_waitcnt(0x0F70);            // vmcnt(0): this work-item's partial has been written through
-        __syncthreads();
-        int* s_last = reinterpret_cast<int*>(lds + G::kLds - 16);
-        if (tid == 0) *s_last = sk_arrive_is_last(p.sk_count + tile, p.sk_id, S) ? 1 : 0;
-        __syncthreads();
-        const int last = *s_last;
+        const SkPartials parked{__builtin_amdgcn_make_buffer_rsrc(p.sk_partial, 0, (int)p.sk_bytes, 0x00020000),
+                                (wv * (XTM * TNE * 64) + lane) * 16};
+        parked.park((tile * S + split) * kSlotBytes, out);
+        const bool last = sk_arrive(reinterpret_cast<int*>(lds + G::kLds - 16), p.sk_count, tile, p.sk_id, S);
         __syncthreads();                               // (s_last has been read by everyone: the epilogue reuses the array)
         if (!last) return;
         // sum over the splits in the order 0 .. S - 1, this workgroup's own share from its registers (the same bits it parked)
@@ -371,8 +296,6 @@ conv_gemm_hlx_kernel(GemmConv p) {
         for (int tm = 0; tm < XTM; ++tm)
 #pragma unroll
             for (int tn = 0; tn < TNE; ++tn) { own[tm][tn] = out[tm][tn]; out[tm][tn] = f32x4{0.f, 0.f, 0.f, 0.f}; }
-        constexpr int kBatch = 10;   // 16-byte loads issued back to back (device-coherent round trips)
-        static_assert((XTM * TNE) % kBatch == 0, "whole batches");
         for (int g = 0; g < S; ++g) {
             if (g == split) {
 #pragma unroll
@@ -382,18 +305,9 @@ conv_gemm_hlx_kernel(GemmConv p) {
                 continue;
             }
             const int so = (tile * S + g) * kSlotBytes;
-#pragma unroll
-            for (int b0 = 0; b0 < XTM * TNE; b0 += kBatch) {
-                u32x4 t[kBatch];
-#pragma unroll
-                for (int j = 0; j < kBatch; ++j) t[j] = __builtin_amdgcn_raw_buffer_load_b128(rs_p, lane_off + (b0 + j) * 1024, so, kSc1);
-                __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-                for (int j = 0; j < kBatch; ++j) out[(b0 + j) / TNE][(b0 + j) % TNE] += __builtin_bit_cast(f32x4, t[j]);
-                __builtin_amdgcn_sched_barrier(0);
-            }
+            DCN_SK_ADD_PARKED(parked, so, out, TNE, XTM * TNE, 10);
         }
-        if (tid == 0) atomicExch(p.sk_count + tile, 0ull);
+        sk_release(p.sk_count + tile);
     }
     gemm_epilogue16<XTM, TNE, XR, BN>(p, out, mt, nt, wm, wm * 80, cb, scratch);
 }

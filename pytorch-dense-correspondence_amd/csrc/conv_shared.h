@@ -5,10 +5,12 @@
 #include <cstdlib>
 
 #include "dcn_common.h"
+#include "f16_split.h"
 
 namespace dcnconv {
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
+typedef float f32x4_t __attribute__((ext_vector_type(4)));
 
 constexpr int NT = 256;
 
@@ -91,6 +93,69 @@ __device__ __forceinline__ bool sk_arrive_is_last(unsigned long long* cnt, unsig
         if (seen == old) return (int)(unsigned)(nv & 0xffffffffull) == contributors;
         old = seen;
     }
+}
+
+// ---- The park-and-complete protocol of every kernel that splits the K range of a tile over workgroups: the stream-K pass of
+// conv_f16_kernels.hip and conv_hl_kernels.hip, the K splits of conv_hlx_kernels.hip.  The parked partials travel between
+// workgroups on different XCDs (separate L2s), so they are written and read with device-coherent accesses (sc1:
+// write-through / L2-bypassing) and ordered against the arrival word by counter waits only -- NO device-scope fence: a
+// release / acquire fence writes back and invalidates the whole L2 of the XCD under the 31 other CUs that are in the middle of
+// their K loops (measured: +50 us per launch, profiles/r2b_ab_fence_variant.txt).
+//   1. park: every lane stores its float4 pieces of the partial tile, 16 bytes each, 1 KB per wave-instruction, in fragment order
+//      -- piece pc at slot offset `so` + lane_off + 1024 pc (SkPartials::park for accumulators of 16 x 16 tiles;
+//      conv_f16_kernels.hip cuts its 32 x 32 tiles into such pieces itself).
+//      sk_arrive: waits until the lane's stores are written through; the workgroup then counts itself into the tile's arrival
+//      word counts[word].  True for the last arriver.  The answer passes from work-item 0 to the others through *s_last, a word
+//      of LDS the caller owns (inside its one array where a second __shared__ object would cost the K loop its counted waits,
+//      conv_hl_kernels.hip); the caller synchronises before it reuses that memory.
+//   2. the last arriver clears its accumulators and adds the slot of every contributor, ITS OWN INCLUDED (or adds its own share
+//      from its registers in the slot's place: the same bits), in the fixed order of the contributors: loads in batches issued
+//      back to back, then added (DCN_SK_ADD_PARKED; conv_f16_kernels.hip has the same loop over its own pieces) -- left to itself
+//      the compiler waits for every 4 loads, and every wait is a device-coherent round trip on the critical path of the launch.
+//      Deterministic.
+//   3. sk_release: the arrival word back to 0, so that a replay of the same captured launch starts clean.
+constexpr int kSkDeviceScope = 16;   // cache-policy bit of buffer loads / stores: device scope (sc1)
+
+// the parked partials of a launch as one lane sees them: buffer resource over them, the lane's byte offset inside a slot
+struct SkPartials {
+    __amdgpu_buffer_rsrc_t rs;
+    int lane_off;
+
+    // the lane's R x C accumulator tiles of 16 x 16 (float4 each): piece pc = tile (pc / C, pc % C)
+    template <int R, int C>
+    __device__ __forceinline__ void park(int so, const f32x4_t (&acc)[R][C]) const {
+#pragma unroll
+        for (int pc = 0; pc < R * C; ++pc)
+            __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(dcnsplit::u32x4, acc[pc / C][pc % C]), rs, lane_off + pc * 1024, so,
+                                                   kSkDeviceScope);
+    }
+};
+// acc (R x C tiles, as SkPartials::park stores them) += the slot parked at `so`, BATCH loads at a time.
+// (A macro: as an inlined function the same loop leaves the loop-carried values of the stream-K kernels of
+// conv_hl_kernels.hip in another order, and their K loops come out scheduled differently -- tools/code_object_diff.py.)
+#define DCN_SK_ADD_PARKED(parked, so, acc, C, PIECES, BATCH)                                                                   \
+    do {                                                                                                                        \
+        static_assert((PIECES) % (BATCH) == 0, "whole batches");                                                                \
+        _Pragma("unroll") for (int b0_ = 0; b0_ < (PIECES); b0_ += (BATCH)) {                                                   \
+            dcnsplit::u32x4 t_[BATCH];                                                                                          \
+            _Pragma("unroll") for (int j_ = 0; j_ < (BATCH); ++j_)                                                              \
+                t_[j_] = __builtin_amdgcn_raw_buffer_load_b128((parked).rs, (parked).lane_off + (b0_ + j_) * 1024, (so), dcnconv::kSkDeviceScope); \
+            __builtin_amdgcn_sched_barrier(0);                                                                                  \
+            _Pragma("unroll") for (int j_ = 0; j_ < (BATCH); ++j_)                                                              \
+                (acc)[(b0_ + j_) / (C)][(b0_ + j_) % (C)] += __builtin_bit_cast(dcnconv::f32x4_t, t_[j_]);                         \
+            __builtin_amdgcn_sched_barrier(0);                                                                                  \
+        }                                                                                                                       \
+    } while (0)
+__device__ __forceinline__ bool sk_arrive(int* s_last, unsigned long long* counts, int word, unsigned id, int contributors) {
+    __builtin_amdgcn_s_waitcnt(0x0F70);                // vmcnt(0): this work-item's partial has been written through
+    __syncthreads();
+    if (threadIdx.x == 0) *s_last = sk_arrive_is_last(counts + word, id, contributors) ? 1 : 0;
+    __syncthreads();
+    return *s_last != 0;
+}
+
+__device__ __forceinline__ void sk_release(unsigned long long* cnt) {
+    if (threadIdx.x == 0) atomicExch(cnt, 0ull);
 }
 
 // id of a stream-K launch with in-launch completion (process-wide, never 0; defined in conv_f16_kernels.hip)
@@ -251,7 +316,6 @@ __device__ __forceinline__ void gemm_epilogue(const GemmConv& p, f32x16 (&acc)[T
 // TM16 x TN16 tiles at tile-relative row `row0` / column `col0` of the BM x BN workgroup tile (mt, nt); the workgroup has TWO
 // wavefronts along M (`wm` = 0 / 1: the fixed order of the statistics).  + bias, + residual gradient, per-M-tile batch-norm
 // partial statistics (sum, sum of squares, max |x| of the accumulators).  `red`: >= 6 BN floats of LDS, free to use.
-typedef float f32x4_t __attribute__((ext_vector_type(4)));
 template <int TM16, int TN16, int BM, int BN>
 __device__ __forceinline__ void gemm_epilogue16(const GemmConv& p, f32x4_t (&out)[TM16][TN16], int mt, int nt, int wm, int row0, int col0,
                                                 float* red) {

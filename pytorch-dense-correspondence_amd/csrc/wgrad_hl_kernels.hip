@@ -23,31 +23,26 @@
 // Half-tiles in the order the phases first need them, as in the forward kernel: H0 = A_0, H1 = B_0, H2 = B_1, H3 = A_1 with
 //     A_i = the dy channels {128 g + 64 i + [0, 64)} (g = 0, 1: local chunk a = 2 g + t),  B_j = the x columns
 //     {64 wn + 32 j + [0, 32)} (wn = 0..3: local chunk b = wn)
-// and the LDS-DMA discipline / WAR / RAW argument of conv_hl_kernels.hip verbatim.  Pixel ranges are split over workgroups
+// and the LDS-DMA discipline / WAR / RAW argument of conv_hl_kernels.hip verbatim (the LDS-DMA load, the raw barrier and the
+// MFMA burst themselves: see conv_hl32.h).  Pixel ranges are split over workgroups
 // (whole 32-pixel stages), partial slabs are summed by the fixed-order reduce kernel of the other wgrad kernels:
 // bit-reproducible.
 #include <algorithm>
 #include <type_traits>
 
-#include "conv_shared.h"
+#include "conv_hl32.h"
 #include "dcn_tuning.h"
-#include "f16_split.h"
 
 namespace {
 
 using namespace dcnconv;
 using namespace dcnsplit;
 
-typedef __attribute__((address_space(3))) void* whl_lds_ptr;
 typedef short s4v __attribute__((ext_vector_type(4)));
 
-constexpr int kOob = (int)0x80000000;
 constexpr int kStage = 65536;   // bytes per 32-pixel stage: A_0 | A_1 | B_0 | B_1, each [32 pixels][512 B]
 constexpr int WPX = 32;         // pixels per stage
 
-__device__ __forceinline__ void glds16(__amdgpu_buffer_rsrc_t rs, void* lds_dst, int voffset, int soffset) {
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (whl_lds_ptr)lds_dst, 16, voffset, soffset, 0, 0);
-}
 // four pixels of one channel (see the header): the transposing 8-byte LDS read
 __device__ __forceinline__ s4v lds_tr4(const unsigned char* p) {
     return __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s4v*)p);
@@ -211,18 +206,10 @@ conv_wgrad_hl_kernel(WgradHl p) {
     };
     auto mfma_quadrant = [&](int i, int j) {
         if (p.setprio) __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-        for (int pt = 0; pt < 3; ++pt)
-#pragma unroll
-            for (int rb = 0; rb < 4; ++rb)
-#pragma unroll
-                for (int cb = 0; cb < 2; ++cb)
-                    acc[4 * i + rb][2 * j + cb] = __builtin_amdgcn_mfma_f32_16x16x32_f16(pt == 0 ? fa[rb][1] : fa[rb][0],
-                                                                                         pt == 1 ? fb[cb][1] : fb[cb][0],
-                                                                                         acc[4 * i + rb][2 * j + cb], 0, 0, 0);
+        hl32_mfma3<4, 2>(fa, fb, acc, 4 * i, 2 * j);
         if (p.setprio) __builtin_amdgcn_s_setprio(0);
     };
-    auto bar = [&]() { __builtin_amdgcn_sched_barrier(0); __builtin_amdgcn_s_barrier(); __builtin_amdgcn_sched_barrier(0); };
+    auto bar = [&]() { raw_barrier(); };
     auto phase = [&](auto more_tag, int buf, int ph) {
         constexpr bool MORE = decltype(more_tag)::value;
         const int qi = ph >> 1, qj = (ph == 1 || ph == 2) ? 1 : 0;
@@ -489,9 +476,7 @@ conv_wgrad_hlr_kernel(WgradHlr p) {
             __builtin_amdgcn_sched_barrier(0);
             DCN_WAIT_VMCNT(0);
         }
-        __builtin_amdgcn_sched_barrier(0);
-        __builtin_amdgcn_s_barrier();
-        __builtin_amdgcn_sched_barrier(0);
+        raw_barrier();
         va = abase + buf * G::kStageBytes;
         DCN_OPAQUE_INT(va);
 #pragma unroll
@@ -661,9 +646,7 @@ conv_wgrad_hlrp_kernel(WgradHlr p) {
             __builtin_amdgcn_sched_barrier(0);
             DCN_WAIT_VMCNT(0);
         }
-        __builtin_amdgcn_sched_barrier(0);
-        __builtin_amdgcn_s_barrier();
-        __builtin_amdgcn_sched_barrier(0);
+        raw_barrier();
         va = abase + buf * RP_STAGE;
         DCN_OPAQUE_INT(va);
 #pragma unroll
