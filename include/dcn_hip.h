@@ -1134,6 +1134,19 @@ int dcn_descriptor_statistics_combine(int n, int d, const float* per_image, cons
  *       others are zero_loss()); type -1 none.
  *       15 the type of the first pair that is not empty (-1 when all are).
  *     One launch of one workgroup.  B >= 1, row >= 0 (the caller keeps it below the rows allocated).
+ *
+ *     Data parallel: G ranks of B pairs each; the global batch is the G B pairs in (rank, pair) order.  Every rank gathers
+ *     all ranks' types (and, for the log, all ranks' rows) in rank order and runs the two entries below on them, so that every
+ *     rank takes the same decision and writes the same row without a host read.
+ * 13e. dcn_train_advance_ranks: 13a's state transition over the G B types of types_all int32 [G][B] (active = N > 0 with
+ *     n_r = #{p : types_all[r][p] != -1}, N = sum of n_r; the same code as 13a: bit for bit its floats), and
+ *     weight_out[0] = N > 0 ? (float)((double)n_rank / (double)N) : 0.0f -- this rank's share of the non-empty pairs, the
+ *     factor of its loss with which the SUM of the ranks' gradients is the gradient of the mean over all non-empty pairs.
+ *     One launch of one work-item.  G >= 1, B >= 1, G B < 2^31, 0 <= rank < G, the rest as 13a.
+ * 13f. dcn_train_log_ranks: 13d's row over the global batch.  gathered float [G][1 + 5 B]: rank r's weighted loss
+ *     (loss_r * w_r), then its terms [B][5].  Columns 0 - 3 and 5 - 15 are 13d's over the G B terms and types in (rank, pair)
+ *     order (the same code); column 4 is the sum of the G weighted losses, added in rank order in double.
+ *     One launch of one workgroup.  G >= 1, B >= 1, G B < 2^31, row >= 0.
  * ===================================================================================================== */
 struct dcn_train_state {
     int32_t active;         /* this iteration counts (set by dcn_train_advance) */
@@ -1155,6 +1168,12 @@ int dcn_guarded_copy(int n, void* const* dst, const void* const* src, const int6
                      const struct dcn_train_state* state, int when_active, void* stream);
 int dcn_train_log(double* history, int64_t row, int64_t iteration, const struct dcn_train_state* state, const float* loss,
                   const float* terms, const int32_t* types, int B, void* stream);
+int dcn_train_advance_ranks(struct dcn_train_state* state, const int32_t* types_all /* [G][B] */, int G, int B, int rank,
+                            float* weight_out /* [1] */, int64_t iteration, int64_t steps_between_decay, double decay,
+                            double beta1, double beta2, void* stream);
+int dcn_train_log_ranks(double* history, int64_t row, int64_t iteration, const struct dcn_train_state* state,
+                        const float* gathered /* [G][1 + 5 B] */, const int32_t* types_all /* [G][B] */, int G, int B,
+                        void* stream);
 
 /* =====================================================================================================
  * 14. Evaluation curves -- what the reference does with a column of an evaluation table:

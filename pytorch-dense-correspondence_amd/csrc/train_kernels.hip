@@ -7,18 +7,19 @@
 //                                             state->active per workgroup; an inactive workgroup touches nothing
 //   guarded_copy_kernel         < 100 KB      the batch-norm buffers of a skipped iteration put back (108 small buffers)
 //   train_log_kernel            1 workgroup   one 128-byte row of the history: reads 5 B floats and B types
+// and, for G data-parallel ranks that have gathered their types and their log rows in rank order (section 13e, 13f), the same
+// rules over the G B pairs of the global batch, so that every rank takes the same decision and writes the same row:
+//   train_advance_ranks_kernel  1 work-item   reads G B types; the state transition above and this rank's share n_rank / N
+//   train_log_ranks_kernel      1 workgroup   reads G (1 + 5 B) floats and G B types
 #include "adam_update.h"
 
 namespace {
 
 typedef struct dcn_train_state TrainState;
 
-__global__ void __launch_bounds__(64)
-train_advance_kernel(TrainState* __restrict__ state, const int32_t* __restrict__ types, int B, int64_t iteration,
-                     int64_t steps_between_decay, double decay, double beta1, double beta2) {
-    if (threadIdx.x != 0 || blockIdx.x != 0) return;
-    int active = 0;
-    for (int p = 0; p < B; ++p) active |= (types[p] != -1);
+// the state transition of one iteration (13a), by the one work-item that owns the state
+__device__ __forceinline__ void advance_state(TrainState* __restrict__ state, int active, int64_t iteration,
+                                              int64_t steps_between_decay, double decay, double beta1, double beta2) {
     state->active = active;
     if (!active) {
         state->num_skipped += 1;
@@ -34,6 +35,36 @@ train_advance_kernel(TrainState* __restrict__ state, const int32_t* __restrict__
     state->step_size = step_size;
     state->bc2_sqrt = bc2_sqrt;
     state->num_active += 1;
+}
+
+// pairs that are not empty among n types
+__device__ __forceinline__ int count_non_empty(const int32_t* __restrict__ types, int n) {
+    int count = 0;
+    for (int p = 0; p < n; ++p) count += (types[p] != -1);
+    return count;
+}
+
+__global__ void __launch_bounds__(64)
+train_advance_kernel(TrainState* __restrict__ state, const int32_t* __restrict__ types, int B, int64_t iteration,
+                     int64_t steps_between_decay, double decay, double beta1, double beta2) {
+    if (threadIdx.x != 0 || blockIdx.x != 0) return;
+    advance_state(state, count_non_empty(types, B) > 0, iteration, steps_between_decay, decay, beta1, beta2);
+}
+
+__global__ void __launch_bounds__(64)
+train_advance_ranks_kernel(TrainState* __restrict__ state, const int32_t* __restrict__ types_all, int G, int B, int rank,
+                           float* __restrict__ weight_out, int64_t iteration, int64_t steps_between_decay, double decay,
+                           double beta1, double beta2) {
+    if (threadIdx.x != 0 || blockIdx.x != 0) return;
+    int64_t total = 0;
+    int mine = 0;
+    for (int r = 0; r < G; ++r) {
+        const int n = count_non_empty(types_all + (size_t)r * B, B);
+        total += n;
+        if (r == rank) mine = n;
+    }
+    advance_state(state, total > 0, iteration, steps_between_decay, decay, beta1, beta2);
+    weight_out[0] = total > 0 ? (float)((double)mine / (double)total) : 0.0f;      // rounded once
 }
 
 __global__ void __launch_bounds__(256)
@@ -69,25 +100,27 @@ __device__ __forceinline__ unsigned composed_terms(int type) {
     return 0u;
 }
 
-__global__ void __launch_bounds__(64)
-train_log_kernel(double* __restrict__ history, int64_t row, int64_t iteration, const TrainState* __restrict__ state,
-                 const float* __restrict__ loss, const float* __restrict__ terms, const int32_t* __restrict__ types, int B) {
-    double* out = history + row * DCN_TRAIN_LOG_COLUMNS;
-    const int k = (int)threadIdx.x;
+// One history row (13d) by work-items 0 .. 5 of a workgroup, over G groups of B pairs in (group, pair) order: the terms of pair
+// (r, p) are the five floats at terms + r * group_stride + 5 p, its type is types[r * B + p]; column 4 is the caller's.
+__device__ __forceinline__ void log_row(double* __restrict__ out, int k, int64_t iteration, const TrainState* __restrict__ state,
+                                        const float* __restrict__ terms, size_t group_stride, const int32_t* __restrict__ types,
+                                        int G, int B, double loss) {
     if (k < 5) {                               // term k: pairs in order, in double
         double sum = 0.0;
         int count = 0;
-        for (int p = 0; p < B; ++p) {
-            if (composed_terms(types[p]) >> k & 1u) {
-                sum += (double)terms[(size_t)p * 5 + k];
-                ++count;
+        for (int r = 0; r < G; ++r) {
+            for (int p = 0; p < B; ++p) {
+                if (composed_terms(types[(size_t)r * B + p]) >> k & 1u) {
+                    sum += (double)terms[r * group_stride + (size_t)p * 5 + k];
+                    ++count;
+                }
             }
         }
         out[5 + 2 * k] = count ? sum / (double)count : 0.0;
         out[6 + 2 * k] = (double)count;
     } else if (k == 5) {
         int valid = 0, first = -1;
-        for (int p = 0; p < B; ++p) {
+        for (int p = 0; p < G * B; ++p) {
             const int ty = types[p];
             if (ty >= 0 && ty < DCN_LOSS_NUM_TYPES) ++valid;
             if (first < 0 && ty != -1) first = ty;
@@ -96,9 +129,28 @@ train_log_kernel(double* __restrict__ history, int64_t row, int64_t iteration, c
         out[1] = (double)state->active;
         out[2] = state->lr;
         out[3] = (double)valid;
-        out[4] = (double)loss[0];
+        out[4] = loss;
         out[15] = (double)first;
     }
+}
+
+__global__ void __launch_bounds__(64)
+train_log_kernel(double* __restrict__ history, int64_t row, int64_t iteration, const TrainState* __restrict__ state,
+                 const float* __restrict__ loss, const float* __restrict__ terms, const int32_t* __restrict__ types, int B) {
+    const int k = (int)threadIdx.x;
+    log_row(history + row * DCN_TRAIN_LOG_COLUMNS, k, iteration, state, terms, 0, types, 1, B, k == 5 ? (double)loss[0] : 0.0);
+}
+
+// gathered float [G][1 + 5 B]: every rank's weighted loss, then its terms
+__global__ void __launch_bounds__(64)
+train_log_ranks_kernel(double* __restrict__ history, int64_t row, int64_t iteration, const TrainState* __restrict__ state,
+                       const float* __restrict__ gathered, const int32_t* __restrict__ types_all, int G, int B) {
+    const int k = (int)threadIdx.x;
+    const size_t stride = 1 + (size_t)5 * B;
+    double loss = 0.0;
+    if (k == 5)
+        for (int r = 0; r < G; ++r) loss += (double)gathered[r * stride];           // in rank order
+    log_row(history + row * DCN_TRAIN_LOG_COLUMNS, k, iteration, state, gathered + 1, stride, types_all, G, B, loss);
 }
 
 }  // namespace
@@ -109,6 +161,17 @@ extern "C" int dcn_train_advance(struct dcn_train_state* state, const int32_t* t
     if (!dcn::adam_hyperparameters_valid(beta1, beta2, 0., 0.)) return DCN_E_INVALID;
     hipLaunchKernelGGL(train_advance_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, state, types, B, iteration,
                        steps_between_decay, decay, beta1, beta2);
+    return dcn::check_launch();
+}
+
+extern "C" int dcn_train_advance_ranks(struct dcn_train_state* state, const int32_t* types_all, int G, int B, int rank,
+                                       float* weight_out, int64_t iteration, int64_t steps_between_decay, double decay,
+                                       double beta1, double beta2, void* stream) {
+    if (!state || !types_all || !weight_out || G < 1 || B < 1 || rank < 0 || rank >= G) return DCN_E_INVALID;
+    if ((int64_t)G * B > 0x7fffffff || steps_between_decay < 1 || !(decay >= 0.)) return DCN_E_INVALID;
+    if (!dcn::adam_hyperparameters_valid(beta1, beta2, 0., 0.)) return DCN_E_INVALID;
+    hipLaunchKernelGGL(train_advance_ranks_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, state, types_all, G, B, rank,
+                       weight_out, iteration, steps_between_decay, decay, beta1, beta2);
     return dcn::check_launch();
 }
 
@@ -156,5 +219,14 @@ extern "C" int dcn_train_log(double* history, int64_t row, int64_t iteration, co
     if (!history || !state || !loss || !terms || !types || B < 1 || row < 0) return DCN_E_INVALID;
     hipLaunchKernelGGL(train_log_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, history, row, iteration, state, loss, terms,
                        types, B);
+    return dcn::check_launch();
+}
+
+extern "C" int dcn_train_log_ranks(double* history, int64_t row, int64_t iteration, const struct dcn_train_state* state,
+                                   const float* gathered, const int32_t* types_all, int G, int B, void* stream) {
+    if (!history || !state || !gathered || !types_all || G < 1 || B < 1 || row < 0) return DCN_E_INVALID;
+    if ((int64_t)G * B > 0x7fffffff) return DCN_E_INVALID;
+    hipLaunchKernelGGL(train_log_ranks_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, history, row, iteration, state,
+                       gathered, types_all, G, B);
     return dcn::check_launch();
 }

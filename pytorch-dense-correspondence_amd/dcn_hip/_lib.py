@@ -241,6 +241,9 @@ SYMBOLS = {
                                       ctypes.c_double, ctypes.c_double, ctypes.c_double, c_void_p, c_void_p]),
     "dcn_guarded_copy": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
     "dcn_train_log": (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
+    "dcn_train_advance_ranks": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_int64, c_int64, ctypes.c_double,
+                                        ctypes.c_double, ctypes.c_double, c_void_p]),
+    "dcn_train_log_ranks": (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p]),
     "dcn_eval_curves": (c_int, [c_int, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_int] + [c_void_p] * 5),
 }
 

@@ -16,15 +16,25 @@ D=3): ``p.grad`` are views into it and autograd accumulates in place.  Two sched
   while the compute stream is still working on buckets k+1..: only the last, small bucket's collective is exposed.
   ``all_reduce_mean`` then just joins the communication stream.  xGMI is point-to-point (7 links per GPU), a ring
   all-reduce of 85 MB on 8 GPUs moves 2 * 7/8 * 85 MB per GPU over one link pair: ~1 ms unhidden, ~0.05 ms exposed here.
+
+``FlatGradients(reduce="sum")`` adds instead of averaging, for ``dcn_hip.train.StoreTrainer(gradients=...)``, which weights every
+rank's loss with its share of the non-empty pairs on the device; ``gather_ranks`` is that trainer's small all-gather.
 """
 import torch
 import torch.distributed as dist
 
 
 class FlatGradients(object):
-    """Owns the flat gradient buffer of ``module`` and averages it across ranks."""
+    """Owns the flat gradient buffer of ``module`` and averages it across ranks.
 
-    def __init__(self, module, process_group=None, bucketed=None, single_rank_collectives=False):
+    ``reduce``: "mean" (the default: every rank's gradient divided by the world size, then summed) or "sum" (summed, no
+    division: for a caller that has weighted every rank's loss itself, as ``dcn_hip.train.StoreTrainer(gradients=...)`` does
+    with the rank's share of the non-empty pairs).  Both schedules honour it."""
+
+    def __init__(self, module, process_group=None, bucketed=None, single_rank_collectives=False, reduce="mean"):
+        if reduce not in ("mean", "sum"):
+            raise ValueError("FlatGradients: reduce must be 'mean' or 'sum', got %r" % (reduce,))
+        self.reduce = reduce
         self.params = [p for p in module.parameters() if p.requires_grad]
         if not self.params:
             raise ValueError("module has no trainable parameters")
@@ -144,7 +154,7 @@ class FlatGradients(object):
                 with torch.cuda.stream(comm):
                     src = engine_flat[lo:hi]
                     if self._collective(world):
-                        if world > 1:
+                        if world > 1 and self.reduce == "mean":
                             src.div_(world)
                         dist.all_reduce(src, op=dist.ReduceOp.SUM, group=self.group)   # enqueued; `comm` is ordered behind it
                         self.stats["bucket_collectives"] += 1
@@ -153,7 +163,7 @@ class FlatGradients(object):
             for lo, hi in plan.grad_buckets:
                 src = engine_flat[lo:hi]
                 if self._collective(world):
-                    if world > 1:
+                    if world > 1 and self.reduce == "mean":
                         src.div_(world)
                     dist.all_reduce(src, op=dist.ReduceOp.SUM, group=self.group)
                     self.stats["bucket_collectives"] += 1
@@ -162,7 +172,7 @@ class FlatGradients(object):
         self.stats["bucketed_steps"] += 1
 
     def all_reduce_mean(self, async_op=False):
-        """Average over ranks.  After a bucketed backward this only joins the communication stream; otherwise ONE
+        """Average over ranks (``reduce="sum"``: add).  After a bucketed backward this only joins the communication stream; otherwise ONE
         collective over the whole buffer.  No-op when torch.distributed is not initialised / world size 1 (apart from
         re-installing detached views)."""
         if self._bucket_step:
@@ -178,7 +188,7 @@ class FlatGradients(object):
         if not self._collective(world):
             return None
         self.stats["monolithic_steps"] += 1
-        if world > 1:
+        if world > 1 and self.reduce == "mean":
             self.flat.div_(world)
         return dist.all_reduce(self.flat, op=dist.ReduceOp.SUM, group=self.group, async_op=async_op)
 
@@ -189,3 +199,32 @@ def broadcast_module(module, src=0, process_group=None):
         return
     for t in list(module.parameters()) + list(module.buffers()):
         dist.broadcast(t.data, src=src, group=process_group)
+
+
+class _Done(object):
+    """The handle of a gather that needed no collective"""
+
+    def wait(self):
+        return True
+
+
+def gather_ranks(tensor, process_group=None, single_rank_collectives=False, async_op=False):
+    """``tensor`` (contiguous, the same shape and dtype on every rank) of every rank, in rank order, in ONE collective ->
+    a tensor [world, *tensor.shape] on ``tensor``'s device; with ``async_op`` -> (that tensor, a handle whose ``wait()``
+    orders the current stream, or with gloo the host, behind the collective), so that work enqueued in between does not wait
+    for it.  Without a process group, or with a world of one, it is a copy and no collective is issued -- unless
+    ``single_rank_collectives`` asks for the collective all the same (the RCCL path on a single GPU, as in ``FlatGradients``)."""
+    if not tensor.is_contiguous():
+        raise ValueError("gather_ranks: a contiguous tensor, got strides %s" % (tensor.stride(),))
+    initialised = dist.is_available() and dist.is_initialized()
+    world = dist.get_world_size(process_group) if initialised else 1
+    out = torch.empty((world,) + tuple(tensor.shape), dtype=tensor.dtype, device=tensor.device)
+    work = None
+    if world > 1 or (single_rank_collectives and initialised):
+        if dist.get_backend(process_group) == "nccl":
+            work = dist.all_gather_into_tensor(out, tensor.detach(), group=process_group, async_op=async_op)
+        else:       # gloo: the list form, its outputs the rows of `out`
+            work = dist.all_gather(list(out.unbind(0)), tensor.detach(), group=process_group, async_op=async_op)
+    else:
+        out[0].copy_(tensor.detach())
+    return (out, work if work is not None else _Done()) if async_op else out

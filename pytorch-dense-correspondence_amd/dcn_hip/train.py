@@ -100,6 +100,31 @@ class TrainState(object):
                                           self.steps_between_decay, self.decay, self.betas[0], self.betas[1], _lib.stream_ptr())
         _lib.check(rc, "dcn_train_advance")
 
+    def _check_types_all(self, types_all):
+        if not torch.is_tensor(types_all) or types_all.dtype != torch.int32:
+            raise TypeError("types_all must be an int32 tensor [G, B] (every rank's SampleBatch.type), got %s"
+                            % (types_all.dtype if torch.is_tensor(types_all) else type(types_all).__name__))
+        if types_all.device != self.buf.device:
+            raise ValueError("types_all is on %s, the training state on %s" % (types_all.device, self.buf.device))
+        if types_all.dim() != 2 or types_all.numel() < 1 or not types_all.is_contiguous():
+            raise ValueError("types_all must be a contiguous tensor [G, B]: one row per rank, one entry per pair")
+        return int(types_all.shape[0]), int(types_all.shape[1])
+
+    def advance_ranks(self, types_all, rank, weight_out, iteration):
+        """``advance`` for G data-parallel ranks: active = any pair of ANY rank is not empty (types_all int32 [G, B], gathered
+        in rank order), the same schedule and step count on every rank; weight_out (one device float) receives this rank's
+        share n_rank / N of the non-empty pairs, 0 when there is none."""
+        G, B = self._check_types_all(types_all)
+        if not torch.is_tensor(weight_out) or weight_out.dtype != torch.float32 or weight_out.numel() != 1 \
+                or weight_out.device != self.buf.device:
+            raise ValueError("weight_out: one float32 on %s" % self.buf.device)
+        if not 0 <= int(rank) < G:
+            raise ValueError("rank %d of %d" % (rank, G))
+        rc = _lib.get().dcn_train_advance_ranks(ctypes.c_void_p(self.state_ptr()), _lib.ptr(types_all), G, B, int(rank),
+                                                _lib.ptr(weight_out), int(iteration), self.steps_between_decay, self.decay,
+                                                self.betas[0], self.betas[1], _lib.stream_ptr())
+        _lib.check(rc, "dcn_train_advance_ranks")
+
     def _bn_tables(self, dcn):
         bufs = list(dcn.buffers())
         bn = self._bn
@@ -143,6 +168,21 @@ class TrainState(object):
                                       ctypes.c_void_p(self.state_ptr()), _lib.ptr(loss.detach()), _lib.ptr(terms.detach()),
                                       _lib.ptr(types), B, _lib.stream_ptr())
         _lib.check(rc, "dcn_train_log")
+        self.rows += 1
+
+    def log_ranks(self, iteration, gathered, types_all):
+        """``log`` over the global batch of G ranks: gathered float32 [G, 1 + 5 B] (every rank's weighted loss, then its terms),
+        types_all int32 [G, B], both in rank order.  Column 4 is the sum of the weighted losses: the loss of the global batch."""
+        G, B = self._check_types_all(types_all)
+        if not torch.is_tensor(gathered) or gathered.dtype != torch.float32 or tuple(gathered.shape) != (G, 1 + 5 * B) \
+                or not gathered.is_contiguous():
+            raise ValueError("gathered: contiguous float32 [G, 1 + 5 B] = [%d, %d]" % (G, 1 + 5 * B))
+        _lib.require_device(gathered, types_all)
+        self._ensure_rows(self.rows + 1)
+        rc = _lib.get().dcn_train_log_ranks(ctypes.c_void_p(self._history_ptr()), self.rows, int(iteration),
+                                            ctypes.c_void_p(self.state_ptr()), _lib.ptr(gathered), _lib.ptr(types_all), G, B,
+                                            _lib.stream_ptr())
+        _lib.check(rc, "dcn_train_log_ranks")
         self.rows += 1
 
     # ---- the host's reads
@@ -307,10 +347,22 @@ class StoreTrainer(object):
     skipped, as the reference skips it.
 
     The logging dict is the reference's: ``update_plots`` appends learning_rate, match_loss, masked_non_match_loss and
-    background_non_match_loss only (its other ``train`` lists stay empty); ``history`` holds every row in full."""
+    background_non_match_loss only (its other ``train`` lists stay empty); ``history`` holds every row in full.
+
+    DATA PARALLEL (``gradients=``: a ``dcn_hip.distributed.FlatGradients(dcn, reduce="sum")`` attached to the optimizer; one
+    process per GPU, every rank with its own store or its own generator and ``host_rng`` seeds, the same batch size B): the
+    global batch is the G B pairs of all ranks.  Every iteration the ranks gather their types (one small collective, waited for
+    after the forward pass), ``TrainState.advance_ranks`` takes the SAME decision on every rank -- the iteration counts when any
+    pair of any rank is not empty -- and gives the rank its share w = n_rank / N of the non-empty pairs; the backward pass is
+    seeded with ``loss * w`` and the gradients are SUMMED over the ranks: the gradient of the mean over all non-empty pairs of
+    the global batch.  A second small collective gathers the ranks' log rows, and every rank writes the same history row.  Every
+    rank issues the same collectives in the same order whatever the device decided, and still reads nothing back.  Batch-norm
+    statistics stay per rank; ``run()`` writes files on ``save_rank`` only.  ``dcn_hip.distributed.broadcast_module`` before
+    the first iteration is the caller's job."""
 
     def __init__(self, dcn, pcl, store, config, *, optimizer=None, generator=None, host_rng=None, logging_dir=None,
-                 batch_size=None, per_pair_types=True, synthetic_multi_object=False, validation=None):
+                 batch_size=None, per_pair_types=True, synthetic_multi_object=False, validation=None, gradients=None,
+                 save_rank=0):
         t = config["training"]
         self.dcn, self.pcl, self.store, self.config = dcn, pcl, store, config
         self.generator, self.host_rng = generator, host_rng
@@ -320,16 +372,23 @@ class StoreTrainer(object):
         self.logging_rate = int(t.get("logging_rate", 0) or 0)
         if optimizer is None:
             optimizer = GuardedAdam(dcn.parameters(), lr=float(t["learning_rate"]), weight_decay=float(t["weight_decay"]))
+            if gradients is not None and hasattr(gradients, "attach"):
+                gradients.attach(optimizer)      # (the trainer's own optimizer: nobody else could have attached it)
         if not isinstance(optimizer, GuardedAdam):
             raise TypeError("StoreTrainer needs a dcn_hip.optim.GuardedAdam (the update is skipped on the device), got %s"
                             % type(optimizer).__name__)
         self.optimizer = optimizer
+        self.gradients, self.save_rank = gradients, int(save_rank)
+        self.world, self.rank = 1, 0
         self._refuse_distributed()
+        if gradients is not None:
+            self._accept_gradients()
         device = next(dcn.parameters()).device
         self.state = TrainState(device, optimizer.param_groups[0]["lr"], t["steps_between_learning_rate_decay"],
                                 t["learning_rate_decay"], betas=optimizer.param_groups[0]["betas"],
                                 rows=self.num_iterations + 64)
         optimizer.bind(self.state)
+        self._weight = torch.zeros((), dtype=torch.float32, device=device) if gradients is not None else None
         self.logging_dir = logging_dir
         self.logging_dict = empty_logging_dict()
         self.history = np.zeros((0, LOG_COLUMNS))
@@ -348,10 +407,42 @@ class StoreTrainer(object):
         self._validation_board_rows = 0
 
     def _refuse_distributed(self):
+        if self.gradients is not None:
+            return
         owners = [m for m in self.dcn.modules() if getattr(m, "_flat_grad_owner", None) is not None]
         if getattr(self.optimizer, "_flat_gradients", None) is not None or owners:
             raise NotImplementedError("StoreTrainer: dcn_hip.distributed gradients are attached; a skip decision that is "
                                       "consistent across ranks is not implemented")
+
+    def _accept_gradients(self):
+        """``gradients=``: the checks of the constructor, and once, on the host, that the ranks agree on B and the world size."""
+        import torch.distributed as dist
+        from .distributed import FlatGradients
+        g = self.gradients
+        if not isinstance(g, FlatGradients):
+            raise TypeError("gradients must be a dcn_hip.distributed.FlatGradients, got %s" % type(g).__name__)
+        if g.reduce != "sum":
+            raise ValueError("StoreTrainer: gradients must be FlatGradients(..., reduce='sum'), got reduce=%r: every rank's loss "
+                             "is weighted with its share of the non-empty pairs, the gradients are added" % (g.reduce,))
+        mine = [p for p in self.dcn.parameters() if p.requires_grad]
+        if len(mine) != len(g.params) or any(a is not b for a, b in zip(mine, g.params)):
+            raise ValueError("StoreTrainer: gradients does not own the parameters of dcn")
+        if getattr(self.optimizer, "_flat_gradients", None) is not g:
+            raise ValueError("StoreTrainer: gradients is not attached to the optimizer (gradients.attach(optimizer))")
+        owners = [m for m in self.dcn.modules() if getattr(m, "_flat_grad_owner", None) not in (None, g)]
+        if owners:
+            raise ValueError("StoreTrainer: another FlatGradients is installed on dcn")
+        if dist.is_available() and dist.is_initialized():
+            self.world, self.rank = dist.get_world_size(g.group), dist.get_rank(g.group)
+        if self.world > 1:
+            said = [None] * self.world
+            dist.all_gather_object(said, (self.batch_size, self.world), group=g.group)
+            if any(x != said[0] for x in said):
+                raise ValueError("StoreTrainer: the ranks disagree on (batch size, world size): %s" % (said,))
+
+    def _gather(self, tensor, async_op=False):
+        from .distributed import gather_ranks
+        return gather_ranks(tensor, self.gradients.group, self.gradients.single_rank_collectives, async_op=async_op)
 
     # ---- one iteration: nothing here reads the device
     def iteration(self, iteration):
@@ -365,6 +456,8 @@ class StoreTrainer(object):
         from dense_correspondence.loss_functions import loss_composer
         B = int(sb.type.numel())
         dcn, state = self.dcn, self.state
+        if self.gradients is not None:
+            return self._step_on_batch_ranks(sb, iteration)
         state.advance(sb.type, iteration)
         self.optimizer.zero_grad()
         state.snapshot_bn(dcn)
@@ -375,6 +468,32 @@ class StoreTrainer(object):
         self.optimizer.step(state)
         state.restore_bn_if_skipped(dcn)
         state.log(iteration, loss, terms, sb.type)
+        self.last = (loss.detach(), terms, num_valid, sb)
+        return loss
+
+    def _step_on_batch_ranks(self, sb, iteration):
+        """The data-parallel iteration.  Two collectives of a few bytes besides the gradients'; the host's control flow does not
+        depend on what the device finds, so the ranks' collective sequences cannot go out of step."""
+        from dense_correspondence.loss_functions import loss_composer
+        B = int(sb.type.numel())
+        if B != self.batch_size:
+            raise ValueError("StoreTrainer: a batch of %d pairs, the ranks agreed on %d" % (B, self.batch_size))
+        dcn, state, grads = self.dcn, self.state, self.gradients
+        types_all, gathered_types = self._gather(sb.type, async_op=True)       # waited for behind the forward pass
+        self.optimizer.zero_grad()
+        state.snapshot_bn(dcn)
+        ya, yb = dcn.forward_pair(sb.input_a, sb.input_b)
+        loss, terms, _, num_valid = loss_composer.get_loss_mixed(self.pcl, dcn.process_network_output(ya, B),
+                                                                 dcn.process_network_output(yb, B), sb.device_lists())
+        gathered_types.wait()
+        state.advance_ranks(types_all, self.rank, self._weight, iteration)
+        weighted = loss * self._weight
+        weighted.backward()
+        grads.all_reduce_mean()                  # reduce="sum"; the join of a bucketed backward
+        self.optimizer.step(state)
+        state.restore_bn_if_skipped(dcn)
+        row = torch.cat([weighted.detach().reshape(1), terms.detach().reshape(-1)])
+        state.log_ranks(iteration, self._gather(row), types_all)
         self.last = (loss.detach(), terms, num_valid, sb)
         return loss
 
@@ -394,7 +513,7 @@ class StoreTrainer(object):
         if self.validation is not None:
             self.validation_history = self.validation.read()       # one more copy at a save point
             self.logging_dict["validation"] = self.validation.logging_dict(self.validation_history)
-        if self.logging_dir is not None:
+        if self.logging_dir is not None and self.rank == self.save_rank:
             if self._board is None:
                 import tensorboard_logger
                 self._board = tensorboard_logger.Logger(os.path.join(self.logging_dir, "tensorboard"))
@@ -447,10 +566,11 @@ class StoreTrainer(object):
         host reads ``active`` once per further iteration and stops, with a final save, at the first active one.
         -> the logging dict."""
         self._refuse_distributed()
+        writes = self.logging_dir is not None and self.rank == self.save_rank      # (reads happen on every rank alike)
         start = int(loss_current_iteration)
         max_num_iterations = self.num_iterations + start
         self.dcn.train()
-        if self.logging_dir is not None:
+        if writes:
             self.save_configs()
             if start == 0:
                 self.save_network(0)
@@ -463,7 +583,7 @@ class StoreTrainer(object):
             snap = None
             if self.logging_dir is not None and self.save_rate > 0 and it % self.save_rate == 0:
                 snap = self.read_log()
-                if snap.active:
+                if snap.active and writes:
                     self.save_network(it, snap, self.logging_dict)
             if self.logging_rate and it % self.logging_rate == 0:
                 logging.info("Training on iteration %d of %d" % (it, max_num_iterations))
@@ -474,6 +594,6 @@ class StoreTrainer(object):
                 if not snap.active:
                     continue
                 logging.info("Finished testing after %d iterations" % max_num_iterations)
-                if self.logging_dir is not None and not saved:
+                if writes and not saved:
                     self.save_network(it, snap, self.logging_dict)
                 return self.logging_dict
