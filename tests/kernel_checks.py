@@ -97,6 +97,9 @@ def check_dgrad_with_bn_backward(L, dev, n, h, w, cin, cout, k, dil, groups=1, w
     assert rel_err(bp[:, :, 0].sum(0), bd.grad) < 2e-5
     assert rel_err(bp[:, :, 1].sum(0), gd.grad) < 2e-5
     assert rel_err(bp[:, :, 2].amax(0), g_ref.abs().amax((0, 1, 2))) < 1e-5
+    xg64 = x.double().reshape(groups, rpg, cin)                           # column 3: max |xhat| per channel (over the groups' tiles)
+    xhat = (xg64 - xg64.mean(1, keepdim=True)) / torch.sqrt(xg64.var(1, unbiased=False, keepdim=True) + 1e-5)
+    assert rel_err(bp[:, :, 3].amax(0), xhat.abs().amax((0, 1))) < 1e-5
     out = {"masked_grad": e_g, "mtiles": mt}
     if groups == 1:
         dgam = torch.empty(cin, device=dev)

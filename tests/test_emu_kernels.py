@@ -231,6 +231,7 @@ def test_conv_f16x3_forward_dgrad(L, case, tile_m, sk, dcn_env):
         assert rel_err(outb, refn * big) < 3e-6, big
     assert rel_err(part.sum(0)[0], refn.sum((0, 1, 2))) < 1e-5
     assert rel_err(part.sum(0)[1], (refn ** 2).sum((0, 1, 2))) < 1e-5
+    assert rel_err(part[:, 2].amax(0), refn.abs().amax((0, 1, 2))) < 5e-6   # max |x| per channel: the input of bn_finalize's bound
     # dgrad with a TINY gradient tensor (1e-7 scale): the abs-max driven power-of-two pre-scale keeps it inside fp16
     dout = torch.randn(n, hout, wout, cout, generator=g) * 1e-7
     ref.backward(dout.permute(0, 3, 1, 2))
