@@ -1217,6 +1217,80 @@ int dcn_eval_curves(int c, int64_t rows, int64_t ld, const double* values /* [c]
                     int num_bins, int64_t* cumcount /* [c][num_bins] */, double* cdf /* [c][num_bins] */,
                     double* summary /* [c][8] */, int32_t* status /* [1], OR of all curves */, void* stream);
 
+/* =====================================================================================================
+ * 15. Qualitative evaluation -- descriptor pictures and distance heat maps: the arithmetic of
+ *     plot_descriptor_colormaps (dense_correspondence/evaluation/evaluation.py:530-601) with the three normalisations of
+ *     dense_correspondence/evaluation/plotting.py:5-87, and of compute_gaussian_kernel_heatmap_from_norm_diffs
+ *     (dense_correspondence_manipulation/utils/visualization.py:27-31).  Nothing OpenCV draws.
+ *     res_a, res_b float [p][h * w][d] (res_b may be NULL: one image per "pair"), mask_a, mask_b uint8 [p][h * w] or NULL
+ *     (non-zero counts as 1).  1 <= p <= 1024, 1 <= d <= 64, h * w < 2^31.  No floating-point atomics: bit-identical from run
+ *     to run.  No host synchronisation.
+ *
+ * 15a. dcn_descriptor_ranges: every image read once.
+ *       image_ranges float [2][p][4][d]   per image (a's, then b's) and channel: min, max over the image; min, max over the
+ *                                         products x * m that are non-zero by numpy's test (-0.0 and 0.0 are left out, NaN
+ *                                         takes part: a zero under the mask is skipped, a non-finite value OUTSIDE the mask is
+ *                                         inf * 0 = NaN) -- plotting.py:59-75.  A NaN among the values makes the min and the max
+ *                                         NaN (np.min / np.max); without masks, or with no such product, rows 2 and 3 are NaN.
+ *       pair_ranges float [p][4][d]       the two images' rows combined by Python's min(a, b) / max(a, b), "b if b < a else a"
+ *                                         (:43-44, :77-78): a NaN in image a stays, a NaN in image b alone is dropped.
+ *       scalar_ranges float [2][p][2]     res.min(), res.max() over all channels of an image
+ *       status int32 [p]                  DCN_PICTURE_EMPTY_RANGE: a channel of an image of the pair has no non-zero product
+ *                                         (the reference raises ValueError from np.min of an empty array)
+ *     Two launches: partials of at most 256 workgroups per image, then one workgroup per pair that folds them in a fixed order.
+ * 15b. dcn_descriptor_normalize: one launch that writes up to two families of outputs (say the unmasked and the masked row of
+ *     the reference's figure), each by its mode:
+ *       DCN_NORM_PAIR          (x - both_min) / (both_max - both_min) in fp32, pair_ranges rows 0, 1        (:28-50)
+ *       DCN_NORM_MASKED_PAIR   the same with rows 2, 3, then * m, in fp32                                   (:52-87)
+ *       DCN_NORM_STATS         v = clip((double)x, min, max); (v - min) / ((max - min) + 1e-10) in float64 with stats
+ *                              double [2][d] (min, then max), the output float64                            (:5-26)
+ *       DCN_NORM_STATS_MASKED  the same on the fp32 product x * m, the result times m     (evaluation.py:585-598)
+ *       DCN_NORM_SCALAR        (x - res_min) / ((res_max - res_min) + 1e-10f) in fp32 with scalar_ranges    (:5-26, stats None)
+ *     every operation rounded on its own.  normed [2][p][h * w][d] (float, double for the STATS modes) and / or picture: the
+ *     bytes matplotlib's imshow shows for the float image, uint8(255 * clip(v, 0, 1)) truncated with the product in the
+ *     precision of v; a NaN gives 0 (matplotlib's own byte for it is not pinned).  A picture shows picture_channels = 3 image
+ *     channels channel[0..2] as [h * w][3] or picture_channels = 1 channel as [h * w]; the picture of (side, pair) starts at
+ *     picture + side * side_stride + pair * pair_stride bytes, on any byte boundary: whole aligned dwords are stored, at most
+ *     3 + 3 bytes per picture singly.  Two families with pictures show the same channels.
+ * 15c. dcn_heat_maps: rows grouped by pair through offsets int64 [p + 1] exactly as dcn_best_match_pairs (section 11c).
+ *     out uint8 [max_rows][h * w]: uint8(exp(-dist / variance) * 255) with dist the fp32 distance of section 4 (fma in
+ *     channel order, sqrtf), the quotient and the product in fp32, the exponential computed in float64 from the fp32 quotient
+ *     and rounded to fp32 once, truncated; a NaN distance gives 0.  With colour_table uint8 [256][3]: out uint8
+ *     [max_rows][h * w][3] = colour_table[that byte].  An image is read once whatever the number of rows.  Rows from
+ *     offsets[p] on are left UNTOUCHED.  status int32 [1] (DCN_EVAL_BAD_OFFSETS); workspace: DCN_HEAT_WORKSPACE_BYTES.  variance > 0.
+ *     The formula is evaluated exactly once per level: a one-workgroup launch finds, by bisection over the float bit patterns,
+ *     the 255 squared distances at which the byte steps (every operation of the formula is monotone), and the pixel loop
+ *     compares against them -- the same bytes, without a float64 exponential per pixel.
+ * ===================================================================================================== */
+#define DCN_PICTURE_EMPTY_RANGE 1
+#define DCN_HEAT_WORKSPACE_BYTES 2048
+#define DCN_NORM_NONE 0
+#define DCN_NORM_PAIR 1
+#define DCN_NORM_MASKED_PAIR 2
+#define DCN_NORM_STATS 3
+#define DCN_NORM_STATS_MASKED 4
+#define DCN_NORM_SCALAR 5
+struct dcn_picture_family {
+    int32_t mode;               /* DCN_NORM_* */
+    int32_t picture_channels;   /* 1 or 3 (read when picture != NULL) */
+    int32_t channel[3];
+    int32_t reserved;
+    const double* stats;        /* [2][d] for the STATS modes */
+    void* normed;               /* or NULL */
+    void* picture;              /* or NULL */
+    int64_t side_stride, pair_stride;
+};
+size_t dcn_descriptor_ranges_workspace(int p, int h, int w, int d);
+int dcn_descriptor_ranges(int p, int h, int w, int d, const float* res_a, const float* res_b, const uint8_t* mask_a,
+                          const uint8_t* mask_b, float* image_ranges, float* pair_ranges, float* scalar_ranges,
+                          int32_t* status, void* workspace, void* stream);
+int dcn_descriptor_normalize(int p, int h, int w, int d, const float* res_a, const float* res_b, const uint8_t* mask_a,
+                             const uint8_t* mask_b, const float* pair_ranges, const float* scalar_ranges,
+                             const struct dcn_picture_family* families /* [2] */, void* stream);
+int dcn_heat_maps(int p, int h, int w, int d, const float* res_b, const float* queries, const int64_t* offsets,
+                  int64_t max_rows, float variance, const uint8_t* colour_table, uint8_t* out, int32_t* status,
+                  void* workspace, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

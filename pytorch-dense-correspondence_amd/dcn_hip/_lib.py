@@ -37,6 +37,13 @@ class FrameStoreDesc(ctypes.Structure):
                                    "object_scenes", "multi_scenes", "scene_cams", "poses")]
 
 
+class PictureFamily(ctypes.Structure):
+    """struct dcn_picture_family"""
+    _fields_ = [("mode", ctypes.c_int32), ("picture_channels", ctypes.c_int32), ("channel", ctypes.c_int32 * 3),
+                ("reserved", ctypes.c_int32), ("stats", c_void_p), ("normed", c_void_p), ("picture", c_void_p),
+                ("side_stride", c_int64), ("pair_stride", c_int64)]
+
+
 SYMBOLS = {
     # name: (restype, argtypes)
     "dcn_version": (c_char_p, []),
@@ -245,6 +252,11 @@ SYMBOLS = {
                                         ctypes.c_double, ctypes.c_double, c_void_p]),
     "dcn_train_log_ranks": (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p]),
     "dcn_eval_curves": (c_int, [c_int, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_int] + [c_void_p] * 5),
+    "dcn_descriptor_ranges_workspace": (c_size_t, [c_int, c_int, c_int, c_int]),
+    "dcn_descriptor_ranges": (c_int, [c_int, c_int, c_int, c_int] + [c_void_p] * 10),
+    "dcn_descriptor_normalize": (c_int, [c_int, c_int, c_int, c_int] + [c_void_p] * 6 + [ctypes.POINTER(PictureFamily * 2),
+                                                                                        c_void_p]),
+    "dcn_heat_maps": (c_int, [c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int64, c_float] + [c_void_p] * 5),
 }
 
 ERRORS = {-1: "DCN_E_INVALID (bad argument)", -2: "DCN_E_LAUNCH (kernel launch failed)",

@@ -34,7 +34,12 @@ kernel of csrc/crossscene_kernels.hip) is for.
 (evaluation.py:305-337): pairs of frames of two different objects (``choose_object_pairs``), pixels sampled from mask a and
 their best matches over the whole of image b (``evaluate_object_pairs``: ``across_object_queries`` + ``best_match_pairs``).
 
-One module per table -- pairs, across_objects, cross_scene, keypoints, descstats, curves -- over the steps they share (_chain);
+``evaluate_network_qualitative`` (csrc/picture_kernels.hip) is the qualitative part, ``evaluate_network_qualitative``
+(evaluation.py:1979-2070): per image pair the descriptor pictures of ``plot_descriptor_colormaps`` (``descriptor_pictures`` over
+``normalize_descriptor``, ``normalize_descriptor_pair``, ``normalize_masked_descriptor_pair``), sampled pixels with their best
+matches, and the distance heat maps of the heat-map tool (``heat_maps``) -- the arithmetic only, nothing OpenCV draws.
+
+One module per table -- pairs, across_objects, cross_scene, keypoints, descstats, curves, pictures -- over the steps they share (_chain);
 every name is also reachable as ``dcn_hip.evaluate.<name>``.
 """
 from .. import augment as _aug  # noqa: F401
@@ -57,3 +62,7 @@ from .descstats import (STAT_FIELDS, STAT_SETS, choose_frames, combine_descripto
 from .curves import (CURVE_DROP_NAN, CURVE_EMPTY, CURVE_FIELDS, CURVE_NAN, CURVE_NONFINITE, CURVE_SUMMARY,  # noqa: F401
                      MAX_CURVE_BINS, MAX_CURVES, EvalCurves, area_above_curve, cumulative_frequencies, curves_to_host,
                      evaluation_curves, write_stats_yaml)
+from .pictures import (EMPTY_RANGE, HEATMAP_KERNEL_VARIANCE, QUALITATIVE_COLUMNS, DescriptorPictures, HeatMaps,  # noqa: F401
+                       Normalized, QualitativeResult, Ranges, choose_qualitative_pairs, colour_table, descriptor_pictures,
+                       descriptor_ranges, evaluate_network_qualitative, heat_maps, normalize_descriptor,
+                       normalize_descriptor_pair, normalize_masked_descriptor_pair, pictures_to_host, save_qualitative)
