@@ -532,6 +532,44 @@ bool ensure_side(dcn_plan& p) {
     }
     return p.side_state == 1;
 }
+// the events behind dcn_plan_stream_wait_grad_bucket (created by the first backward call)
+bool ensure_bucket_events(dcn_plan& p) {
+    if (p.bucket_state == 0) {
+        bool ok = true;
+        p.ev_bucket.assign(p.bucket_first.size(), nullptr);
+        for (hipEvent_t& ev : p.ev_bucket) ok = ok && hipEventCreateWithFlags(&ev, hipEventDisableTiming) == hipSuccess;
+        ok = ok && hipEventCreateWithFlags(&p.ev_bucket_side, hipEventDisableTiming) == hipSuccess;
+        p.bucket_state = ok ? 1 : -1;
+    }
+    return p.bucket_state == 1;
+}
+
+// One pass's use of the plan's side stream next to the caller's stream `st`: every event / stream-dependency call goes through
+// here and is checked (a missed dependency is a data race, so a failure must not pass silently: `failed` -> DCN_E_LAUNCH),
+// and an early error return between fork and join must not leave side-stream kernels working on arenas the caller is about
+// to free: the destructor makes the caller's stream wait (through `ev_exit`) for whatever the side stream has been given.
+struct SideFork {
+    dcn_plan& p;
+    hipStream_t st;
+    hipEvent_t ev_exit;
+    bool open = false;     // the side stream has been given work that `st` has not been made to wait for
+    bool failed = false;
+    bool ok(hipError_t e) { if (e != hipSuccess) failed = true; return e == hipSuccess; }
+    bool record(hipEvent_t ev, hipStream_t s) { return ok(hipEventRecord(ev, s)); }
+    bool wait(hipEvent_t ev) { return ok(hipStreamWaitEvent(st, ev, 0)); }   // the caller's stream behind ev
+    // the side stream behind ev (recorded on the caller's stream): what is launched there next is open work
+    bool side_wait(hipEvent_t ev) { open = true; return ok(hipStreamWaitEvent(p.side, ev, 0)); }
+    bool fork(hipEvent_t ev) { return record(ev, st) && side_wait(ev); }
+    // join: the caller's stream behind everything the side stream has been given (record and wait may be apart)
+    bool join_wait(hipEvent_t ev) { const bool done = wait(ev); open = open && !done; return done; }
+    bool join(hipEvent_t ev) { return record(ev, p.side) && join_wait(ev); }
+    ~SideFork() {
+        if (open && hipEventRecord(ev_exit, p.side) == hipSuccess) (void)hipStreamWaitEvent(st, ev_exit, 0);
+    }
+    SideFork(dcn_plan& plan, hipStream_t s, hipEvent_t e) : p(plan), st(s), ev_exit(e) {}
+    SideFork(const SideFork&) = delete;
+    SideFork& operator=(const SideFork&) = delete;
+};
 
 #define DCN_TRY(expr)                    \
     do {                                 \
@@ -977,29 +1015,18 @@ int forward_impl(dcn_plan* plan, const float* image, const float* image_b, const
         hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
         if (hipStreamIsCapturing(st, &cs) != hipSuccess || cs != hipStreamCaptureStatusNone) hoist = false;
     }
-    // an error return between fork and join must not leave side-stream kernels writing into arenas the caller is about to free:
-    // the guard makes the caller's stream wait for whatever the side stream has been given
-    struct ForkGuard {
-        dcn_plan& p;
-        hipStream_t st;
-        bool armed = false;
-        ~ForkGuard() {
-            if (armed && hipEventRecord(p.ev_ws[1], p.side) == hipSuccess) (void)hipStreamWaitEvent(st, p.ev_ws[1], 0);
-        }
-    } fork_guard{p, st};
+    SideFork side(p, st, p.ev_ws[1]);   // (an error return between fork and join: see SideFork)
     if (p.conv_mode == DCN_CONV_F16X3) {
         if (hoist) {
             Run Rs{p, params, (float*)saved, (float*)workspace, p.side, routes};
-            bool ok = hipEventRecord(p.ev_ws[0], st) == hipSuccess && hipStreamWaitEvent(p.side, p.ev_ws[0], 0) == hipSuccess;
-            if (!ok) return DCN_E_LAUNCH;
-            fork_guard.armed = true;
+            if (!side.fork(p.ev_ws[0])) return DCN_E_LAUNCH;
             DCN_TRY(Rs.split_all_weights(false, Rs.Wk(p.w_wstem)));
             DCN_TRY(Rs.split_hl_weights(false));
             Rs.wh_over = Rs.S(p.s_wht); Rs.wl_over = Rs.S(p.s_wlt); Rs.whl_over = Rs.S(p.s_whlt);
             DCN_TRY(Rs.split_all_weights(true, nullptr));
             DCN_TRY(Rs.split_hl_weights(true));
             rec.wt_saved = true;
-            if (hipEventRecord(p.ev_ws[1], p.side) != hipSuccess) return DCN_E_LAUNCH;
+            if (!side.record(p.ev_ws[1], p.side)) return DCN_E_LAUNCH;
         } else {
             DCN_TRY(R.split_all_weights(false, R.Wk(p.w_wstem)));
             DCN_TRY(R.split_hl_weights(false));
@@ -1020,13 +1047,13 @@ int forward_impl(dcn_plan* plan, const float* image, const float* image_b, const
             dcn::launch_maxpool_fwd(R.S(stem.x), R.S(p.s_pool), (unsigned char*)R.S(p.s_argmax), N, stem.d.hout, stem.d.wout, hp,
                                     wp, b.C, st, s, p.groups, R.M(p.s_stem_y));
         } else {
-            dcn::launch_bn_apply(R.S(stem.x), s, nullptr, nullptr, 1, R.S(p.s_stem_y), R.M(p.s_stem_y), b.C, b.rows, p.groups, st);
+            dcn::launch_bn_apply({.x = R.S(stem.x), .stats = s, .C = b.C, .rows = b.rows, .groups = p.groups, .y = R.S(p.s_stem_y),
+                                  .relu_mask = R.M(p.s_stem_y)}, st);
             dcn::launch_maxpool_fwd(R.S(p.s_stem_y), R.S(p.s_pool), (unsigned char*)R.S(p.s_argmax), N, stem.d.hout,
                                     stem.d.wout, hp, wp, b.C, st);
         }
     }
-    if (hoist && hipStreamWaitEvent(st, p.ev_ws[1], 0) != hipSuccess) return DCN_E_LAUNCH;   // join: the weight images are there
-    fork_guard.armed = false;
+    if (hoist && !side.join_wait(p.ev_ws[1])) return DCN_E_LAUNCH;   // join: the weight images are there
     if (training && f16_mode && p.blocks[0].has_hl_in) {   // (the first block's input is the max-pool output: no apply pass writes it)
         const BlockL& b0 = p.blocks[0];
         R.hl_saved.emplace_back(R.S(b0.in), R.S(b0.hl_in));
@@ -1053,8 +1080,9 @@ int forward_impl(dcn_plan* plan, const float* image, const float* image_b, const
                 const bool hl_only = hl && slot && hl == (void*)slot && (b.C % 32) == 0 && dcn::tuning().hl_only_mid != 0 &&
                                      routes[nxt.idx].fwd == Kernel::HL && routes[nxt.idx].wgrad == Kernel::HL;
                 rec.mid_hl_only[nxt.idx] = hl_only ? 1 : 0;
-                dcn::launch_bn_apply(R.S(c.x), s, nullptr, nullptr, 1, hl_only ? nullptr : R.S(blk.mid[i]), R.M(blk.mid[i]), b.C,
-                                     b.rows, p.groups, st, hl, R.A(blk.act_mid[i]));
+                dcn::launch_bn_apply({.x = R.S(c.x), .stats = s, .C = b.C, .rows = b.rows, .groups = p.groups,
+                                      .y = hl_only ? nullptr : R.S(blk.mid[i]), .relu_mask = R.M(blk.mid[i]), .hl_out = hl,
+                                      .hl_absmax = R.A(blk.act_mid[i])}, st);
                 DCN_TRY(R.ensure_saved_hl(R.S(blk.mid[i]), slot, b.rows, b.C, blk.act_mid[i]));
                 cur = R.S(blk.mid[i]);
             } else {
@@ -1071,15 +1099,11 @@ int forward_impl(dcn_plan* plan, const float* image, const float* image_b, const
         void* hl = (training && nb) ? R.hl_image_for(R.S(blk.out), 0, &p.convs[nb->conv[0]], nb->down >= 0 ? &p.convs[nb->down] : nullptr,
                                                      slot)
                                     : nullptr;
-        if (blk.down >= 0) {
-            const ConvL& dc = p.convs[blk.down];
-            const float* sd = R.S(p.bns[dc.bn].stats);
-            dcn::launch_bn_apply(R.S(last.x), sl, R.S(dc.x), sd, 1, R.S(blk.out), R.M(blk.out), bl.C, bl.rows, p.groups, st, hl,
-                                 R.A(blk.act_out));
-        } else {
-            dcn::launch_bn_apply(R.S(last.x), sl, in, nullptr, 1, R.S(blk.out), R.M(blk.out), bl.C, bl.rows, p.groups, st, hl,
-                                 R.A(blk.act_out));
-        }
+        // the residual: the downsample branch through its batch norm, or the block's input as it is
+        const ConvL* dc = blk.down >= 0 ? &p.convs[blk.down] : nullptr;
+        dcn::launch_bn_apply({.x = R.S(last.x), .stats = sl, .C = bl.C, .rows = bl.rows, .groups = p.groups,
+                              .res = dc ? R.S(dc->x) : in, .res_stats = dc ? R.S(p.bns[dc->bn].stats) : nullptr, .y = R.S(blk.out),
+                              .relu_mask = R.M(blk.out), .hl_out = hl, .hl_absmax = R.A(blk.act_out)}, st);
         DCN_TRY(R.ensure_saved_hl(R.S(blk.out), slot, bl.rows, bl.C, blk.act_out));
     }
     }   // !fused_eval
@@ -1122,6 +1146,91 @@ extern "C" int dcn_backbone_forward_pair(dcn_plan* plan, const float* image_a, c
 
 namespace {
 
+// The backward pass's images of the gradient w.r.t. a convolution's output (the dx of a batch-norm backward), and the protocol
+// between their writer and their readers.  The convolution's weight-gradient GEMM reads dx as an image -- pixel-blocked
+// split-fp16 (`blocked`) or hl32 (`hl`, which the hl32 dgrad reads too) -- and only feeds the optimizer, so with overlap on it
+// runs on the plan's side stream while the caller's stream goes on with dgrad(k) -> batch-norm backward(k - 1), which writes
+// the NEXT image.  Hence two slots, taken in turn, and two events per slot:
+//     caller's stream:  take()          wait `read`: the GEMM that read what the slot held two layers ago
+//                       ... the batch-norm backward's apply pass writes the images ...
+//                       wrote()         record `written`
+//     side stream:      read_on_side()  wait `written`, the GEMM, record `read`
+// Overlap off (fp32 mode, profiling, DCN_BACKWARD_OVERLAP=0, inside a graph capture): slot 0 only, no events, readers in line.
+// Three operations touch a slot outside that cycle; each says why it needs no wait.
+struct GradImages {
+    Run& R;
+    SideFork& side;
+    const bool overlap;
+    struct Slot {
+        float* blocked;
+        float* hl;
+        hipEvent_t written, read;
+        const float* blocked_of = nullptr;   // the gradient tensor whose image of each kind the slot holds
+        const float* hl_of = nullptr;
+        bool reader_pending = false;         // `read` has been recorded in this call: the next take() waits on it
+    } slot[2];
+    int cur = 0, taken = 0;
+    GradImages(Run& run, SideFork& fork, bool on)
+        : R(run), side(fork), overlap(on),
+          slot{{R.Wk(R.p.w_dq), R.hlbuf(0), R.p.ev_dq[0], R.p.ev_wg[0]}, {R.Wk(R.p.w_dq2), R.hlbuf(1), R.p.ev_dq[1], R.p.ev_wg[1]}} {}
+
+    Slot& take() {   // the next slot, for writing
+        cur = overlap ? (taken & 1) : 0;
+        ++taken;
+        if (overlap && slot[cur].reader_pending) side.wait(slot[cur].read);
+        return slot[cur];
+    }
+    void wrote(const float* blocked_of, const float* hl_of) {   // what the writer of the taken slot left there (null: no such image)
+        if (overlap) side.record(slot[cur].written, R.st);
+        slot[cur].blocked_of = blocked_of;
+        slot[cur].hl_of = hl_of;
+    }
+    // one weight-gradient launch that reads the current slot: launch(stream)
+    template <class L> int read_on_side(const ConvL& c, L&& launch) {
+        if (!overlap) return R.timed(1, c.flops, [&] { return launch(R.st); });
+        side.side_wait(slot[cur].written);
+        DCN_TRY(launch(R.p.side));
+        side.record(slot[cur].read, R.p.side);
+        slot[cur].reader_pending = true;
+        return DCN_OK;
+    }
+    bool has_blocked(const float* dx) const { return slot[cur].blocked_of == dx; }
+    const float* blocked() const { return slot[cur].blocked; }
+    const float* hl() const { return slot[cur].hl; }
+
+    // The hl32 image of dx for its weight-gradient GEMM, where the batch-norm backward did not write it (DCN_HL_PRODUCERS=0, or
+    // the scoring layer's gradient, which no batch norm produces): split(image) on the caller's stream into the current slot,
+    // then `written` as after any write.  No wait for `read`: the slot was taken by the batch-norm backward that produced dx
+    // (or, for the scoring layer, has not been used in this call), and no reader of it has been launched since that take().
+    template <class S> int hl_for_wgrad(const float* dx, S&& split) {
+        Slot& s = slot[cur];
+        if (s.hl_of == dx) return DCN_OK;
+        DCN_TRY(R.other([&] { return split(s.hl); }));
+        if (overlap) side.record(s.written, R.st);
+        s.hl_of = dx;
+        return DCN_OK;
+    }
+    // The same for dx's hl32 dgrad (inside that launch's profiling bracket).  No wait, no record: the weight gradient of the same
+    // dx comes first; had it read an hl32 image, the image would be there (hl_of == dx), so the side stream's reader of this slot,
+    // if any, reads `blocked`.  What `hl` held before belonged to another tensor, whose reader take() waited for; and the image's
+    // only reader is the dgrad behind it on the caller's stream.
+    template <class S> int hl_for_dgrad(const float* dx, S&& split) {
+        Slot& s = slot[cur];
+        if (s.hl_of == dx) return DCN_OK;
+        DCN_TRY(split(s.hl));
+        s.hl_of = dx;
+        return DCN_OK;
+    }
+    // A gradient that has no pixel-blocked image (only the scoring layer's: every other one comes out of a batch-norm backward):
+    // split(image) and gemm(image, stream) in line on the caller's stream, always through slot 0's buffer, no event.  It is the
+    // first use of the slots in the call -- the side stream has no reader of this call yet, and the call before joined its own.
+    template <class S, class G> int blocked_in_line(const ConvL& c, S&& split, G&& gemm) {
+        float* image = slot[0].blocked;
+        DCN_TRY(R.other([&] { return split(image); }));
+        return R.timed(1, c.flops, [&] { return gemm(image, R.st); });
+    }
+};
+
 // grad_b (optional, grouped plans): the gradient of the second batch's descriptors (images [N/2, N)) when the two
 // gradients of a forward_pair call are separate tensors
 int backward_impl(dcn_plan* plan, const float* grad_descriptors, const float* grad_b, const float* const* params,
@@ -1159,31 +1268,16 @@ int backward_impl(dcn_plan* plan, const float* grad_descriptors, const float* gr
     float* amax = R.Wk(p.w_amax);
     const bool f16 = p.conv_mode == DCN_CONV_F16X3;
 
-    // Overlap (split-fp16 mode, not while launches are being timed one by one): wgrad of layer k only feeds the optimizer,
-    // so it runs on the plan's side stream while the main stream goes on with dgrad(k) -> BN backward(k - 1) -> ...; the
-    // gradient's pixel-blocked image alternates between two buffers and events order writer and reader of each.
-    bool overlap = f16 && !p.prof_on;
-    overlap = overlap && ensure_side(p);
-    if (p.bucket_state == 0) {   // events behind dcn_plan_stream_wait_grad_bucket
-        bool ok = true;
-        p.ev_bucket.assign(p.bucket_first.size(), nullptr);
-        for (hipEvent_t& ev : p.ev_bucket) ok = ok && hipEventCreateWithFlags(&ev, hipEventDisableTiming) == hipSuccess;
-        ok = ok && hipEventCreateWithFlags(&p.ev_bucket_side, hipEventDisableTiming) == hipSuccess;
-        p.bucket_state = ok ? 1 : -1;
-    }
-    // event / stream-dependency calls of the overlap and bucket logic: a failure must not pass silently (a missed
-    // dependency is a data race), so every one is checked
-    int rt_fail = 0;
-    auto RT = [&](hipError_t e) { if (e != hipSuccess) rt_fail = 1; };
-    if (overlap) {   // inside a hipGraph capture the fork / join pattern replays slower than the serial chain (measured): stay serial
+    // Overlap (split-fp16 mode, not while launches are being timed one by one; inside a hipGraph capture the fork / join pattern
+    // replays slower than the serial chain, measured: stay serial): the weight gradients run on the plan's side stream (GradImages)
+    bool overlap = f16 && !p.prof_on && ensure_side(p);
+    if (overlap) {
         hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
         if (hipStreamIsCapturing(st, &cs) != hipSuccess || cs != hipStreamCaptureStatusNone) overlap = false;
     }
-    int n_bn = 0, cur = 0;              // BN-backward launches so far; buffer holding the newest split gradient
-    bool wg_pending[2] = {false, false};
-    float* const dqbuf[2] = {R.Wk(p.w_dq), R.Wk(p.w_dq2)};
-    float* const hlimg[2] = {R.hlbuf(0), R.hlbuf(1)};   // hl32 images of dx, alternating like dqbuf (same events order their users)
-    const float* dq_of = nullptr;       // gradient tensor whose pixel-blocked split copy is in dqbuf[cur]
+    const bool buckets = ensure_bucket_events(p);
+    SideFork side(p, st, p.ev_join);
+    GradImages img(R, side, overlap);
     // BN backward of conv c's batch norm: dy (+ optional relu mask from relu_out) -> dx; g_out optional
     // Fused reduction (split-fp16 mode): the dgrad that produces a batch norm's upstream gradient dy also masks it with the
     // ReLU bits and leaves the per-tile sums of the BN backward reduction in `part` (GemmConv::bnb_*): bn_bwd then only
@@ -1192,68 +1286,53 @@ int backward_impl(dcn_plan* plan, const float* grad_descriptors, const float* gr
     p.fused_bn_bwd = 0;
     const float* red_dy = nullptr;
     int red_tiles = 0;
-    const float* hl_dx_of = nullptr;    // gradient tensor whose hl32 image sits in w_hl (written by the BN backward apply pass)
     // dy2 (optional): the upstream gradient is dy + dy2 -- the residual branch's share, added in the batch norm's streaming
     // passes instead of in the epilogue of the dgrad that produced dy
     auto bn_bwd = [&](const ConvL& c, const float* dy, const float* relu_out, float* dx, float* g_out, const float* dy2 = nullptr) {
         const BnL& b = p.bns[c.bn];
-        const float* s = R.S(b.stats);
         // (the mask bytes the forward wrote next to that activation; relu_out itself is then not read)
         const unsigned char* mask = relu_out ? R.M((size_t)(relu_out - R.saved)) : nullptr;
-        cur = overlap ? (n_bn & 1) : 0;
-        if (overlap && wg_pending[cur]) RT(hipStreamWaitEvent(st, p.ev_wg[cur], 0));   // the wgrad that read this buffer two layers ago
+        GradImages::Slot& slot = img.take();
         const int tiles = (red_dy == dy && dy) ? red_tiles : 0;
         red_dy = nullptr;
         if (tiles > 0) { relu_out = nullptr; mask = nullptr; g_out = nullptr; ++p.fused_bn_bwd; }   // dy is already the masked gradient
-        // the dgrad of this convolution on the hl32 path: the apply pass writes dx as the hl32 image INSTEAD of the fp32 tensor
-        // (wgrad reads the pixel-blocked image, nobody reads the fp32 one)
+        // the images of dx the apply pass writes: the hl32 one where this convolution's dgrad or weight gradient reads it -- the
+        // dgrad: INSTEAD of the fp32 tensor, which nobody else reads --, the pixel-blocked one unless the weight gradient reads hl32
         const bool prod = f16 && dcn::tuning().hl_producers != 0;
-        const bool hl_d = prod && !fuse_red && routes[c.idx].dgrad == Kernel::HL;   // this convolution's dgrad reads the hl32 image
-        const bool hl_w = prod && routes[c.idx].wgrad == Kernel::HL;                // ... its weight gradient too: no pixel-blocked image then
-        hl_dx_of = (hl_d || hl_w) ? dx : nullptr;
-        dcn::launch_bn_bwd(dy, relu_out, mask, R.S(c.x), s, R.P(b.g), b.C, b.rows, p.groups, part, grads[b.g],
-                           grads[b.b], k123, dx, g_out, f16 ? amax + c.idx : nullptr,
-                           (f16 && !hl_w) ? (void*)dqbuf[cur] : nullptr, st, tiles, dy2,
-                           (hl_d || hl_w) ? (void*)hlimg[cur] : nullptr, hl_d ? 0 : 1,
-                           (overlap && dcn::tuning().bn_bwd_lean != 0) ? dcn::tuning().bn_bwd_lean_mask : 0);   // (lean instances beside the side stream's GEMMs)
-        if (overlap) RT(hipEventRecord(p.ev_dq[cur], st));
-        ++n_bn;
-        dq_of = (f16 && !hl_w) ? dx : nullptr;   // the pixel-blocked split copy of this dx now sits in dqbuf[cur]
+        const bool hl_d = prod && !fuse_red && routes[c.idx].dgrad == Kernel::HL;
+        const bool hl_w = prod && routes[c.idx].wgrad == Kernel::HL;
+        const bool want_blocked = f16 && !hl_w, want_hl = hl_d || hl_w;
+        dcn::launch_bn_bwd({.dy = dy, .dy2 = dy2, .relu_out = relu_out, .relu_mask = mask, .x = R.S(c.x), .stats = R.S(b.stats),
+                            .gamma = R.P(b.g), .C = b.C, .rows = b.rows, .groups = p.groups, .partial = part, .k123 = k123,
+                            .reduced_tiles_per_group = tiles, .dgamma = grads[b.g], .dbeta = grads[b.b], .dx = dx, .g_out = g_out,
+                            .absmax = f16 ? amax + c.idx : nullptr, .dq = want_blocked ? slot.blocked : nullptr,
+                            .hl_dx = want_hl ? slot.hl : nullptr, .skip_fp32_dx = hl_d,
+                            // (lean instances beside the side stream's GEMMs)
+                            .lean = (overlap && dcn::tuning().bn_bwd_lean != 0) ? dcn::tuning().bn_bwd_lean_mask : 0}, st);
+        img.wrote(want_blocked ? dx : nullptr, want_hl ? dx : nullptr);
     };
-    // one weight-gradient launch reading buffer `cur`: on the side stream behind that image's writer (ev_wg[cur]: read), or in line
-    auto wgrad_launch = [&](const ConvL& c, auto&& launch) -> int {
-        if (!overlap) return R.timed(1, c.flops, [&] { return launch(st); });
-        RT(hipStreamWaitEvent(p.side, p.ev_dq[cur], 0));
-        DCN_TRY(launch(p.side));
-        RT(hipEventRecord(p.ev_wg[cur], p.side));
-        wg_pending[cur] = true;
-        return DCN_OK;
+    auto split_hl = [&](const ConvL& c, const float* dx, float* image) {
+        return dcn_split_act_hl32(dx, amax + c.idx, image, (int64_t)c.d.n * c.d.hout * c.d.wout, c.d.ldc, st);
     };
     auto wgrad = [&](const ConvL& c, const float* in, const float* dx, float* dw) -> int {
         const Kernel k = routes[c.idx].wgrad;
         if (k == Kernel::FP32) return R.timed(1, c.flops, [&] { return dcn_conv_wgrad(&c.d, in, dx, dw, slab, st); });
         if (k == Kernel::HL) {   // both operands as hl32 tensors: the saved image of the input, the image of dx
-            const float* ximg = R.S(c.hl_x);
-            if (hl_dx_of != dx) {  // (DCN_HL_PRODUCERS=0, or a gradient that no batch-norm backward produced)
-                DCN_TRY(R.other([&] { return dcn_split_act_hl32(dx, amax + c.idx, hlimg[cur], (int64_t)c.d.n * c.d.hout * c.d.wout, c.d.ldc, st); }));
-                if (overlap) RT(hipEventRecord(p.ev_dq[cur], st));
-                hl_dx_of = dx;
-            }
-            return wgrad_launch(c, [&](hipStream_t s) {
-                return dcn_conv_wgrad_hl(&c.d, ximg, R.A(c.in_act), hlimg[cur], amax + c.idx, dw, slab, s);
+            DCN_TRY(img.hl_for_wgrad(dx, [&](float* image) { return split_hl(c, dx, image); }));
+            return img.read_on_side(c, [&](hipStream_t s) {
+                return dcn_conv_wgrad_hl(&c.d, R.S(c.hl_x), R.A(c.in_act), img.hl(), amax + c.idx, dw, slab, s);
             });
         }
         // Kernel::F16.  The activation operand is the fp32 tensor itself, split on the fly inside the kernel: measured faster than a
         // split pass + pre-split operand on every layer of ResNet34 / ResNet50 (the pass costs more than the conversions).
-        if (dq_of != dx) {   // (BN backward emits it directly; only the scoring layer's gradient needs the separate pass)
-            DCN_TRY(R.other([&] { return dcn_split_grad_blocked_f16(dx, c.d.n * c.d.hout * c.d.wout, c.d.ldc, amax + c.idx, dqbuf[0], st); }));
-            return R.timed(1, c.flops, [&] {
-                return dcn_conv_wgrad_f16(&c.d, in, 1, R.A(c.in_act), dqbuf[0], amax + c.idx, dw, slab, st);
-            });
-        }
-        return wgrad_launch(c, [&](hipStream_t s) {
-            return dcn_conv_wgrad_f16(&c.d, in, 1, R.A(c.in_act), dqbuf[cur], amax + c.idx, dw, slab, s);
-        });
+        auto gemm = [&](const float* image, hipStream_t s) {
+            return dcn_conv_wgrad_f16(&c.d, in, 1, R.A(c.in_act), image, amax + c.idx, dw, slab, s);
+        };
+        if (!img.has_blocked(dx))   // (BN backward emits it directly; only the scoring layer's gradient needs the separate pass)
+            return img.blocked_in_line(c, [&](float* image) {
+                return dcn_split_grad_blocked_f16(dx, c.d.n * c.d.hout * c.d.wout, c.d.ldc, amax + c.idx, image, st);
+            }, gemm);
+        return img.read_on_side(c, [&](hipStream_t s) { return gemm(img.blocked(), s); });
     };
     // bn_of: the convolution whose batch norm's backward consumes din as its upstream gradient (din = gradient w.r.t. that
     // batch norm's ReLU'd output `relu_out`), or null
@@ -1280,13 +1359,8 @@ int backward_impl(dcn_plan* plan, const float* grad_descriptors, const float* gr
         }
         if (r.dgrad == Kernel::HL) {
             return R.timed(2, c.flops, [&] {
-                if (hl_dx_of != dx) {
-                    // (the side stream's weight-gradient kernel may still be reading hlimg[cur]: the image is only rewritten when
-                    // it holds another tensor, i.e. after the wait at the top of the bn_bwd that owns the buffer)
-                    DCN_TRY(dcn_split_act_hl32(dx, amax + c.idx, hlimg[cur], (int64_t)c.d.n * c.d.hout * c.d.wout, c.d.ldc, st));
-                    hl_dx_of = dx;
-                }
-                return dcn_conv_dgrad_hl(&c.d, hlimg[cur], R.whl(c), kWeightScale, amax + c.idx, add, din, R.SK(c, 1, Kernel::HL), st);
+                DCN_TRY(img.hl_for_dgrad(dx, [&](float* image) { return split_hl(c, dx, image); }));
+                return dcn_conv_dgrad_hl(&c.d, img.hl(), R.whl(c), kWeightScale, amax + c.idx, add, din, R.SK(c, 1, Kernel::HL), st);
             });
         }
         return R.timed(0, c.flops, [&] {   // (transposed weight images: split_all_weights(true) below)
@@ -1396,12 +1470,9 @@ int backward_impl(dcn_plan* plan, const float* grad_descriptors, const float* gr
         // gradient bucket complete?  (every launch that writes one of its gradients has been enqueued: the side stream's
         // weight-gradient GEMMs are joined into the caller's stream first)
         for (size_t k = 0; k + 1 < p.bucket_block.size(); ++k)
-            if (p.bucket_block[k] == bi && p.bucket_state == 1) {
-                if (overlap) {
-                    RT(hipEventRecord(p.ev_bucket_side, p.side));
-                    RT(hipStreamWaitEvent(st, p.ev_bucket_side, 0));
-                }
-                RT(hipEventRecord(p.ev_bucket[k], st));
+            if (p.bucket_block[k] == bi && buckets) {
+                if (overlap) side.join(p.ev_bucket_side);
+                side.record(p.ev_bucket[k], st);
             }
     }
     // ---- max pool, stem
@@ -1412,13 +1483,10 @@ int backward_impl(dcn_plan* plan, const float* grad_descriptors, const float* gr
                             st, dout_add);   // (the first block's deferred identity gradient joins here)
     bn_bwd(stem, dnext, R.S(p.s_stem_y), dxa, nullptr);
     DCN_TRY(wgrad(stem, R.S(p.s_in4), dxa, R.Wk(p.w_dwstem)));
-    if (overlap) {   // join: everything the side stream produced is ordered before whatever follows on the caller's stream
-        RT(hipEventRecord(p.ev_join, p.side));
-        RT(hipStreamWaitEvent(st, p.ev_join, 0));
-    }
+    if (overlap) side.join(p.ev_join);   // everything the side stream produced is ordered before whatever follows on the caller's stream
     dcn::launch_unpad_c4_to_c3(R.Wk(p.w_dwstem), grads[stem.w], (int64_t)p.base * 49, st);
-    if (p.bucket_state == 1) RT(hipEventRecord(p.ev_bucket.back(), st));   // last bucket: the whole backward pass
-    if (rt_fail) return DCN_E_LAUNCH;
+    if (buckets) side.record(p.ev_bucket.back(), st);   // last bucket: the whole backward pass
+    if (side.failed) return DCN_E_LAUNCH;
     return dcn::check_launch();
 }
 

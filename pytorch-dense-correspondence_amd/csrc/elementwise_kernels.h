@@ -38,30 +38,56 @@ void launch_pad_rows(const float* src, float* dst, int64_t rows, int d, int ld, 
 void launch_bn_finalize(const float* partial, int tiles_per_group, int groups, int C, double count_per_group,
                         const float* gamma, const float* beta, float* rmean, float* rvar, float momentum, float eps,
                         int training, float* stats, float* out_bound, const float* res_bound, hipStream_t st);
-// y = [relu](x*scale1 + shift1 + (res ? (stats2 ? res*scale2 + shift2 : res) : 0))
-// relu_mask (optional, with relu): one byte per float4 of y, bit j = y[4i + j] > 0 (read back by launch_bn_bwd)
-// hl_out (optional, with hl_absmax; C % 32 == 0): y also as the hl32 image of conv_hl_kernels.hip, scaled by the power of two
-// chosen from *hl_absmax (the bound launch_bn_finalize stored for y)
-void launch_bn_apply(const float* x, const float* stats1, const float* res, const float* stats2, int relu, float* y,
-                     unsigned char* relu_mask, int C, int64_t rows, int groups, hipStream_t st, void* hl_out = nullptr,
-                     const float* hl_absmax = nullptr);
+// y = [relu](x*scale + shift + (res ? (res_stats ? res*scale2 + shift2 : res) : 0)).  A call site names what it passes.
+struct BnApplyArgs {
+    const float* x;                       // [rows][C]
+    const float* stats;                   // this batch norm's [groups][4][C]
+    int C;
+    int64_t rows;
+    int groups = 1;
+    int relu = 1;
+    const float* res = nullptr;           // residual, added before the ReLU ...
+    const float* res_stats = nullptr;     // ... through a batch norm of its own (downsample branch), or as it is
+    float* y = nullptr;                   // (optional when hl_out is the only copy anybody reads)
+    unsigned char* relu_mask = nullptr;   // with relu: one byte per float4 of y, bit j = y[4i + j] > 0 (read back by launch_bn_bwd)
+    // y also as the hl32 image of conv_hl_kernels.hip, scaled by the power of two chosen from *hl_absmax (the bound
+    // launch_bn_finalize stored for y).  Both or neither; written only where C % 32 == 0
+    void* hl_out = nullptr;
+    const float* hl_absmax = nullptr;
+};
+void launch_bn_apply(const BnApplyArgs& a, hipStream_t st);
 int bn_bwd_chunks(int64_t rows_per_group);
-// partial: groups*bn_bwd_chunks(rows/groups)*4*C floats, k123: groups*3*C floats.  g_out (nullable) receives the
-// relu-masked dy.  absmax (optional): raised to an upper bound of max |dx|
-// the ReLU mask of dy comes from relu_mask (bytes written by launch_bn_apply) if given, else from relu_out, else none
-void launch_bn_bwd(const float* dy, const float* relu_out, const unsigned char* relu_mask, const float* x, const float* stats,
-                   const float* gamma, int C,
-                   int64_t rows, int groups, float* partial, float* dgamma, float* dbeta, float* k123, float* dx,
-                   float* g_out, float* absmax, void* dq, hipStream_t st,    // dq (optional, with absmax): dx also as the
-                   int reduced_tiles_per_group = 0,                          // pixel-blocked split-fp16 tensor (f16_split.h)
-                   const float* dy2 = nullptr,    // dy2 (optional): the upstream gradient is dy + dy2 (residual branch's share)
-                   void* hl_dx = nullptr,         // hl_dx (optional, with dq; C % 32 == 0): dx also as the hl32 image the pre-split
-                   int keep_dx = 0,               // dgrad reads; the fp32 dx is then NOT written unless keep_dx
-                   int lean = 0);                 // lean: bit mask of the kernels that run their <= 48-VGPR instance -- 1 reduce,
-                                                  // 2 finalize, 4 blocked apply -- with the same bits (DCN_BN_BWD_LEAN)
-// reduced_tiles_per_group > 0: `partial` already holds that many rows per group of per-tile sums, written by the epilogue
-// of the dgrad that produced dy (GemmConv::bnb_partial) -- the reduce pass is skipped; dy is then already ReLU-masked
-// (pass relu_out = relu_mask = nullptr)
+// Batch-norm backward: reduce (skipped with reduced_tiles_per_group) -> finalize -> apply.
+struct BnBwdArgs {
+    const float* dy;
+    const float* dy2 = nullptr;                 // the upstream gradient is dy + dy2 (the residual branch's share)
+    // the ReLU mask of dy comes from relu_mask (bytes written by launch_bn_apply) if given, else from relu_out, else none
+    const float* relu_out = nullptr;
+    const unsigned char* relu_mask = nullptr;
+    const float* x;
+    const float* stats;                         // [groups][4][C]
+    const float* gamma;
+    int C;
+    int64_t rows;
+    int groups = 1;
+    float* partial;                             // groups * bn_bwd_chunks(rows / groups) * 4 * C floats
+    float* k123;                                // groups * 3 * C floats
+    // > 0: `partial` already holds that many rows per group of per-tile sums, written by the epilogue of the dgrad that produced
+    // dy (GemmConv::bnb_partial) -- the reduce pass is skipped; dy is then already ReLU-masked (no relu_out / relu_mask)
+    int reduced_tiles_per_group = 0;
+    float* dgamma;
+    float* dbeta;
+    float* dx;
+    float* g_out = nullptr;                     // receives the ReLU-masked dy
+    float* absmax = nullptr;                    // raised to an upper bound of max |dx|; the two images below need it
+    void* dq = nullptr;                         // dx also as the pixel-blocked split-fp16 tensor (f16_split.h)
+    void* hl_dx = nullptr;                      // dx also as the hl32 image the pre-split dgrad reads (written where C % 32 == 0)
+    bool skip_fp32_dx = false;                  // where the hl32 image is written, dx itself is not (nobody reads it)
+    // bit mask of the kernels that run their <= 48-VGPR instance -- 1 reduce, 2 finalize, 4 blocked apply -- with the same
+    // bits (DCN_BN_BWD_LEAN)
+    int lean = 0;
+};
+void launch_bn_bwd(const BnBwdArgs& a, hipStream_t st);
 void launch_add(const float* a, const float* b, float* out, int64_t n, hipStream_t st);
 
 // bn_stats (optional): [groups][scale C | shift C | mean C | invstd C] of the batch norm whose output is pooled -- `in` is then

@@ -1123,17 +1123,16 @@ void launch_bn_finalize(const float* partial, int tiles_per_group, int groups, i
                        count_per_group, gamma, beta, rmean, rvar, momentum, eps, training, stats, stats + C, stats + 2 * C,
                        stats + 3 * C, 4 * C, out_bound, res_bound);
 }
-void launch_bn_apply(const float* x, const float* stats1, const float* res, const float* stats2, int relu, float* y,
-                     unsigned char* relu_mask, int C, int64_t rows, int groups, hipStream_t st, void* hl_out,
-                     const float* hl_absmax) {
-    const int64_t total4 = rows * (C / 4);
-    if ((C % 32) != 0 || !hl_absmax) hl_out = nullptr;
+void launch_bn_apply(const BnApplyArgs& a, hipStream_t st) {
+    const int C = a.C;
+    const int64_t total4 = a.rows * (C / 4);
+    void* hl_out = ((C % 32) == 0 && a.hl_absmax) ? a.hl_out : nullptr;
     // bytes per element: x (+ the residual) in; y, the hl32 image (the size of y) and a quarter byte of ReLU mask out
-    ObservedLaunch obs(DCN_PROF_BN_APPLY, (double)rows * C * (4.0 + (res ? 4.0 : 0.0) + (y ? 4.0 : 0.0) + (hl_out ? 4.0 : 0.0) +
-                                                             (relu_mask ? 0.25 : 0.0)), st);
-    hipLaunchKernelGGL(bn_apply_kernel, dim3(blocks_for(total4, kGridCap)), dim3(256), 0, st, x, stats1, stats1 + C, res,
-                       stats2, stats2 ? stats2 + C : nullptr, relu, y, relu_mask, C / 4, total4, total4 / groups, 4 * C,
-                       (dcnsplit::u32x2*)hl_out, hl_absmax, tuning().bn_reverse & 1, tuning().bn_nt & 1);
+    ObservedLaunch obs(DCN_PROF_BN_APPLY, (double)a.rows * C * (4.0 + (a.res ? 4.0 : 0.0) + (a.y ? 4.0 : 0.0) + (hl_out ? 4.0 : 0.0) +
+                                                               (a.relu_mask ? 0.25 : 0.0)), st);
+    hipLaunchKernelGGL(bn_apply_kernel, dim3(blocks_for(total4, kGridCap)), dim3(256), 0, st, a.x, a.stats, a.stats + C, a.res,
+                       a.res_stats, a.res_stats ? a.res_stats + C : nullptr, a.relu, a.y, a.relu_mask, C / 4, total4,
+                       total4 / a.groups, 4 * C, (dcnsplit::u32x2*)hl_out, a.hl_absmax, tuning().bn_reverse & 1, tuning().bn_nt & 1);
 }
 int bn_bwd_chunks(int64_t rows_per_group) {
     // enough row chunks that even a 64-channel layer launches >= ~1000 workgroups (HBM-bound pass: fill all 256 CUs)
@@ -1146,21 +1145,32 @@ int bn_bwd_chunks(int64_t rows_per_group) {
     if (chunks < 1) chunks = 1;
     return (int)chunks;
 }
-void launch_bn_bwd(const float* dy, const float* relu_out, const unsigned char* relu_mask, const float* x, const float* stats,
-                   const float* gamma, int C,
-                   int64_t rows, int groups, float* partial, float* dgamma, float* dbeta, float* k123, float* dx,
-                   float* g_out, float* absmax, void* dq, hipStream_t st, int reduced_tiles_per_group, const float* dy2,
-                   void* hl_dx, int keep_dx, int lean) {
-    const int64_t rpg = rows / groups;
-    const float* mean = stats + 2 * C;
-    const float* invstd = stats + 3 * C;
-    int chunks = reduced_tiles_per_group;
+// The blocked apply pass's instance: full, or (lean bit 4) the <= 48-VGPR one -- `deep`: with 2 rows in flight, 3 where the
+// budget allows (DCN_BN_BWD_LEAN_DEPTH > 2 and no pixel-blocked image to keep).  with_dq: the pixel-blocked image is written
+// (defined behind its caller: the order in which the kernel templates are first named is their order in the code object)
+static decltype(&bn_bwd_apply_blocked_kernel) bn_bwd_blocked_apply_instance(int lean, bool deep, int depth, bool with_dq);
+void launch_bn_bwd(const BnBwdArgs& a, hipStream_t st) {
+    const int C = a.C, groups = a.groups, lean = a.lean;
+    const int64_t rows = a.rows, rpg = rows / groups;
+    const float *dy = a.dy, *dy2 = a.dy2, *relu_out = a.relu_out, *x = a.x;
+    const unsigned char* relu_mask = a.relu_mask;
+    const float* mean = a.stats + 2 * C;
+    const float* invstd = a.stats + 3 * C;
+    float *partial = a.partial, *k123 = a.k123, *g_out = a.g_out, *absmax = a.absmax;
+    // the two images of dx (they take the bound in absmax for their scale) and the fp32 tensor: what the apply pass writes
+    void* hl = (a.hl_dx && (C % 32) == 0) ? a.hl_dx : nullptr;
+    void* dq = a.dq;
+    const bool blocked = (dq || hl) && absmax;
+    float* dx = (blocked && hl && a.skip_fp32_dx) ? nullptr : a.dx;
+    int chunks = a.reduced_tiles_per_group;
     // DCN_BN_BWD_LEAN_DEPTH: where the lean blocked apply pass would run, the one with several rows in flight (it takes the ReLU
     // mask as bytes or not at all, and keeps the constants of at most two groups of 512 channels in LDS)
     const int depth = tuning().bn_bwd_lean_depth;
-    const bool deep = depth > 1 && !(relu_out && !relu_mask);
-    // bytes per element read by both streaming passes: dy (+ dy2), x, the ReLU mask byte per float4 (or the activation)
+    const bool deep = depth > 1 && !(relu_out && !relu_mask) && C <= 512 && groups <= 2;
+    // bytes per element read by both streaming passes: dy (+ dy2), x, the ReLU mask byte per float4 (or the activation);
+    // written by the apply pass: every output that is there
     const double in_bytes = 8.0 + (dy2 ? 4.0 : 0.0) + (relu_mask ? 0.25 : (relu_out ? 4.0 : 0.0));
+    const double out_bytes = (dx ? 4.0 : 0.0) + (g_out ? 4.0 : 0.0) + (blocked && dq ? 4.0 : 0.0) + (blocked && hl ? 4.0 : 0.0);
     if (chunks <= 0) {
         chunks = bn_bwd_chunks(rpg);   // per group
         const int rpc = (int)ceil_div64(rpg, chunks);
@@ -1184,29 +1194,27 @@ void launch_bn_bwd(const float* dy, const float* relu_out, const unsigned char* 
         ObservedLaunch obs(DCN_PROF_BN_FINALIZE, 16.0 * (double)chunks * groups * C, st);
         const auto kernel = (lean & 2) ? bn_bwd_finalize_lean_kernel : bn_bwd_finalize_kernel;
         hipLaunchKernelGGL(kernel, dim3(ceil_div(C, 4)), dim3(256), 0, st,
-                           (const float*)partial, chunks, groups, C, (double)rpg, gamma, invstd, 4 * C, dgamma, dbeta, k123, absmax);
+                           (const float*)partial, chunks, groups, C, (double)rpg, a.gamma, invstd, 4 * C, a.dgamma, a.dbeta, k123, absmax);
     }
     const int64_t total4 = rows * (C / 4);
-    if ((dq || (hl_dx && (C % 32) == 0)) && absmax) {
-        const bool hl = hl_dx && (C % 32) == 0;
-        ObservedLaunch obs(DCN_PROF_BN_BWD_APPLY, (double)rows * C * (in_bytes + ((hl && !keep_dx) ? 0.0 : 4.0) + (g_out ? 4.0 : 0.0) +
-                                                                      (dq ? 4.0 : 0.0) + (hl ? 4.0 : 0.0)), st);
-        const bool deep_apply = deep && C <= 512 && groups <= 2;
-        const auto kernel = !(lean & 4) ? bn_bwd_apply_blocked_kernel
-                            : (!deep_apply ? (dq ? bn_bwd_apply_blocked_lean_kernel<true> : bn_bwd_apply_blocked_lean_kernel<false>)
-                               : (dq ? bn_bwd_apply_blocked_deep_kernel<2, true>
-                                     : (depth > 2 ? bn_bwd_apply_blocked_deep_kernel<3, false> : bn_bwd_apply_blocked_deep_kernel<2, false>)));
+    ObservedLaunch obs(DCN_PROF_BN_BWD_APPLY, (double)rows * C * (in_bytes + out_bytes), st);
+    if (blocked) {
+        const auto kernel = bn_bwd_blocked_apply_instance(lean, deep, depth, dq != nullptr);
         hipLaunchKernelGGL(kernel, dim3(blocks_for(((rows + 3) / 4) * (C / 4), kGridCap)), dim3(256), 0, st,
                            dy, dy2, relu_out, relu_mask, x, mean, invstd, (const float*)k123, (const float*)(k123 + C),
-                           (const float*)(k123 + 2 * C), (hl_dx && (C % 32) == 0 && !keep_dx) ? nullptr : dx, g_out,
-                           (dcnsplit::u32x4*)dq, (const float*)absmax, C / 4, rows, rpg, 4 * C, 3 * C,
-                           (C % 32) == 0 ? (dcnsplit::u32x2*)hl_dx : nullptr, (tuning().bn_reverse >> 1) & 1, (tuning().bn_nt >> 1) & 1);
+                           (const float*)(k123 + 2 * C), dx, g_out, (dcnsplit::u32x4*)dq, (const float*)absmax, C / 4, rows, rpg,
+                           4 * C, 3 * C, (dcnsplit::u32x2*)hl, (tuning().bn_reverse >> 1) & 1, (tuning().bn_nt >> 1) & 1);
         return;
     }
-    ObservedLaunch obs(DCN_PROF_BN_BWD_APPLY, (double)rows * C * (in_bytes + 4.0 + (g_out ? 4.0 : 0.0)), st);
     hipLaunchKernelGGL(bn_bwd_apply_kernel, dim3(blocks_for(total4, kGridCap)), dim3(256), 0, st, dy, dy2, relu_out, relu_mask,
                        x, mean, invstd, (const float*)k123, (const float*)(k123 + C), (const float*)(k123 + 2 * C), dx, g_out,
                        C / 4, total4, total4 / groups, 4 * C, 3 * C, (tuning().bn_reverse >> 1) & 1);
+}
+static decltype(&bn_bwd_apply_blocked_kernel) bn_bwd_blocked_apply_instance(int lean, bool deep, int depth, bool with_dq) {
+    if (!(lean & 4)) return bn_bwd_apply_blocked_kernel;
+    if (!deep) return with_dq ? bn_bwd_apply_blocked_lean_kernel<true> : bn_bwd_apply_blocked_lean_kernel<false>;
+    if (!with_dq) return depth > 2 ? bn_bwd_apply_blocked_deep_kernel<3, false> : bn_bwd_apply_blocked_deep_kernel<2, false>;
+    return bn_bwd_apply_blocked_deep_kernel<2, true>;
 }
 void launch_add(const float* a, const float* b, float* out, int64_t n, hipStream_t st) {
     ObservedLaunch obs(DCN_PROF_OTHER, 12.0 * (double)n, st);
@@ -1302,9 +1310,12 @@ extern "C" int dcn_bn_forward(const float* x, const float* bn_partial, int mtile
     hipStream_t st = (hipStream_t)stream;
     dcn::launch_bn_finalize(bn_partial, mtiles, 1, c, (double)rows, gamma, beta, running_mean, running_var, momentum, eps,
                             training, stats, nullptr, nullptr, st);
-    dcn::launch_bn_apply(x, stats, res, nullptr, relu, y, relu_mask, c, rows, 1, st);
+    dcn::launch_bn_apply({.x = x, .stats = stats, .C = c, .rows = rows, .relu = relu, .res = res, .y = y, .relu_mask = relu_mask}, st);
     return dcn::check_launch();
 }
+
+// (the stand-alone entry points run the instances the engine's overlapped backward pass would)
+static int standalone_lean() { return dcn::tuning().bn_bwd_lean ? dcn::tuning().bn_bwd_lean_mask : 0; }
 
 extern "C" size_t dcn_bn_backward_workspace(int64_t rows, int c) {
     if (rows < 1 || c < 4) return 0;
@@ -1318,8 +1329,9 @@ extern "C" int dcn_bn_backward(const float* dy, const unsigned char* relu_mask, 
         return DCN_E_INVALID;
     float* partial = (float*)workspace;
     float* k123 = partial + (size_t)dcn::bn_bwd_chunks(rows) * 4 * c;
-    dcn::launch_bn_bwd(dy, nullptr, relu_mask, x, stats, gamma, c, rows, 1, partial, dgamma, dbeta, k123, dx, g_out, nullptr,
-                       nullptr, (hipStream_t)stream, 0, nullptr, nullptr, 0, dcn::tuning().bn_bwd_lean ? dcn::tuning().bn_bwd_lean_mask : 0);
+    dcn::launch_bn_bwd({.dy = dy, .relu_mask = relu_mask, .x = x, .stats = stats, .gamma = gamma, .C = c, .rows = rows,
+                        .partial = partial, .k123 = k123, .dgamma = dgamma, .dbeta = dbeta, .dx = dx, .g_out = g_out,
+                        .lean = standalone_lean()}, (hipStream_t)stream);
     return dcn::check_launch();
 }
 
@@ -1331,9 +1343,9 @@ extern "C" int dcn_bn_backward_from_partial(const float* dy, const float* bn_par
     if (!dy || !bn_partial || mtiles < 1 || !x || !stats || !gamma || !dgamma || !dbeta || !dx || !workspace || c < 4 ||
         (c % 4) != 0 || rows < 1)
         return DCN_E_INVALID;
-    dcn::launch_bn_bwd(dy, nullptr, nullptr, x, stats, gamma, c, rows, 1, const_cast<float*>(bn_partial), dgamma, dbeta,
-                       (float*)workspace, dx, nullptr, nullptr, nullptr, (hipStream_t)stream, mtiles, nullptr, nullptr, 0,
-                       dcn::tuning().bn_bwd_lean ? dcn::tuning().bn_bwd_lean_mask : 0);
+    dcn::launch_bn_bwd({.dy = dy, .x = x, .stats = stats, .gamma = gamma, .C = c, .rows = rows,
+                        .partial = const_cast<float*>(bn_partial), .k123 = (float*)workspace, .reduced_tiles_per_group = mtiles,
+                        .dgamma = dgamma, .dbeta = dbeta, .dx = dx, .lean = standalone_lean()}, (hipStream_t)stream);
     return dcn::check_launch();
 }
 
@@ -1356,8 +1368,10 @@ extern "C" int dcn_bn_backward_full(const float* dy, const float* dy2, const flo
     if (!dx && !(hl_dx && !keep_dx)) return DCN_E_INVALID;
     float* partial = (float*)workspace;
     float* k123 = partial + (size_t)groups * dcn::bn_bwd_chunks(rows / groups) * 4 * c;
-    dcn::launch_bn_bwd(dy, relu_out, relu_mask, x, stats, gamma, c, rows, groups, partial, dgamma, dbeta, k123, dx, g_out, absmax,
-                       dq, (hipStream_t)stream, 0, dy2, hl_dx, keep_dx, dcn::tuning().bn_bwd_lean ? dcn::tuning().bn_bwd_lean_mask : 0);
+    dcn::launch_bn_bwd({.dy = dy, .dy2 = dy2, .relu_out = relu_out, .relu_mask = relu_mask, .x = x, .stats = stats, .gamma = gamma,
+                        .C = c, .rows = rows, .groups = groups, .partial = partial, .k123 = k123, .dgamma = dgamma, .dbeta = dbeta,
+                        .dx = dx, .g_out = g_out, .absmax = absmax, .dq = dq, .hl_dx = hl_dx, .skip_fp32_dx = !keep_dx,
+                        .lean = standalone_lean()}, (hipStream_t)stream);
     return dcn::check_launch();
 }
 

@@ -1,4 +1,5 @@
 """Shared helpers for the test-suite (not a test module)."""
+import ctypes
 import os
 import sys
 
@@ -21,6 +22,29 @@ def use_emulation_library():
     _lib.load(path)
     assert _lib.is_hostemu()
     return _lib
+
+
+class CallLog(object):
+    """The host emulation's call log (tests/hostemu/hipemu_runtime.cpp): one line per kernel launch, event record and stream
+    wait since the ``with`` block began.  ``lines()`` may be called inside the block, e.g. before and after one engine call."""
+
+    def __init__(self, lib):
+        self.lib = lib
+        lib.hipemu_log_read.restype = ctypes.c_size_t
+        lib.hipemu_log_read.argtypes = [ctypes.c_char_p, ctypes.c_size_t]
+
+    def __enter__(self):
+        self.lib.hipemu_log_begin()
+        return self
+
+    def __exit__(self, *exc):
+        self.lib.hipemu_log_end()
+
+    def lines(self):
+        n = self.lib.hipemu_log_read(None, 0)
+        buf = ctypes.create_string_buffer(n + 1)
+        self.lib.hipemu_log_read(buf, n + 1)
+        return buf.value.decode().splitlines()
 
 
 def use_gfx950_library():

@@ -50,9 +50,17 @@ inline hipError_t hipMalloc(void** p, size_t n) { *p = malloc(n); return *p ? hi
 inline hipError_t hipFree(void* p) { free(p); return hipSuccess; }
 inline hipError_t hipMemset(void* p, int v, size_t n) { memset(p, v, n); return hipSuccess; }
 typedef struct hipemu_event { double t; }* hipEvent_t;
+// Optional call log (hipemu_runtime.cpp: hipemu_log_begin / hipemu_log_read / hipemu_log_end): one text line per kernel
+// launch, event record and stream wait, so that a test can read the SCHEDULE of an engine call.  Off: one flag test per call.
+namespace hipemu {
+extern bool g_log_on;
+void log_launch(const char* kernel, unsigned gx, unsigned gy, unsigned gz, unsigned bx, unsigned by, unsigned bz, hipStream_t st);
+void log_record(hipEvent_t ev, hipStream_t st);
+void log_wait(hipStream_t st, hipEvent_t ev);
+}  // namespace hipemu
 inline hipError_t hipEventCreate(hipEvent_t* e) { *e = new hipemu_event{0.0}; return hipSuccess; }
 inline hipError_t hipEventDestroy(hipEvent_t e) { delete e; return hipSuccess; }
-// (the emulation executes every launch synchronously: streams and cross-stream dependencies are no-ops)
+// (the emulation executes every launch synchronously: streams and cross-stream dependencies are no-ops, but for the call log)
 #define hipStreamNonBlocking 1
 #define hipEventDisableTiming 2
 inline hipError_t hipEventCreateWithFlags(hipEvent_t* e, unsigned) { *e = new hipemu_event{0.0}; return hipSuccess; }
@@ -60,10 +68,16 @@ inline hipError_t hipDeviceGetStreamPriorityRange(int* lo, int* hi) { *lo = 0; *
 inline hipError_t hipGetDevice(int* d) { *d = 0; return hipSuccess; }
 inline hipError_t hipStreamCreateWithPriority(hipStream_t* s, unsigned, int) { *s = (hipStream_t)new int(0); return hipSuccess; }
 inline hipError_t hipStreamDestroy(hipStream_t s) { delete (int*)s; return hipSuccess; }
-inline hipError_t hipStreamWaitEvent(hipStream_t, hipEvent_t, unsigned) { return hipSuccess; }
+inline hipError_t hipStreamWaitEvent(hipStream_t s, hipEvent_t e, unsigned) {
+    if (::hipemu::g_log_on) ::hipemu::log_wait(s, e);
+    return hipSuccess;
+}
 enum hipStreamCaptureStatus { hipStreamCaptureStatusNone = 0, hipStreamCaptureStatusActive = 1 };
 inline hipError_t hipStreamIsCapturing(hipStream_t, hipStreamCaptureStatus* s) { *s = hipStreamCaptureStatusNone; return hipSuccess; }
-inline hipError_t hipEventRecord(hipEvent_t, hipStream_t) { return hipSuccess; }
+inline hipError_t hipEventRecord(hipEvent_t e, hipStream_t s) {
+    if (::hipemu::g_log_on) ::hipemu::log_record(e, s);
+    return hipSuccess;
+}
 inline hipError_t hipEventSynchronize(hipEvent_t) { return hipSuccess; }
 inline hipError_t hipEventElapsedTime(float* ms, hipEvent_t, hipEvent_t) { *ms = 0.f; return hipSuccess; }
 inline hipError_t hipDeviceSynchronize() { return hipSuccess; }
@@ -177,7 +191,9 @@ template <class T> inline T wave_exchange(T v, int src_lane) {
 
 void run_grid(dim3 grid, dim3 block, const std::function<void()>& body);
 
-template <class F> inline void launch(dim3 grid, dim3 block, F&& f) {
+// name: the kernel as written at the launch site (hipLaunchKernelGGL's first argument)
+template <class F> inline void launch(const char* name, dim3 grid, dim3 block, hipStream_t st, F&& f) {
+    if (g_log_on) log_launch(name, grid.x, grid.y, grid.z, block.x, block.y, block.z, st);
     std::function<void()> body(std::forward<F>(f));
     run_grid(grid, block, body);
 }
@@ -191,7 +207,7 @@ template <class F> inline void launch(dim3 grid, dim3 block, F&& f) {
 #define warpSize 64
 
 #define hipLaunchKernelGGL(kernel, grid, block, shmem, stream, ...) \
-    ::hipemu::launch((grid), (block), [=]() { kernel(__VA_ARGS__); })
+    ::hipemu::launch(#kernel, (grid), (block), (hipStream_t)(stream), [=]() { kernel(__VA_ARGS__); })
 
 static inline void __syncthreads() { ::hipemu::block_barrier(); }
 static inline void __threadfence() { __atomic_thread_fence(__ATOMIC_SEQ_CST); }

@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 
 #include <mutex>
+#include <string>
 #include <sys/mman.h>
 
 namespace hipemu {
@@ -144,4 +145,58 @@ void run_grid(dim3 grid, dim3 block, const std::function<void()>& body) {
     for (auto& t : ts) t.join();
 }
 
+// ---- call log.  Streams and events are reported as small numbers in order of first appearance since hipemu_log_begin; the
+// null stream (what the CPU tests pass as the caller's stream) is always 0, so two runs can be compared as text.
+bool g_log_on = false;
+namespace {
+std::mutex g_log_mu;
+std::string g_log_text;
+std::vector<const void*> g_log_streams, g_log_events;
+int log_id(std::vector<const void*>& seen, const void* p) {
+    for (size_t i = 0; i < seen.size(); ++i)
+        if (seen[i] == p) return (int)i;
+    seen.push_back(p);
+    return (int)seen.size() - 1;
+}
+void log_line(const char* fmt, const char* name, const unsigned* d, const void* st, const void* ev) {
+    char line[512];
+    std::lock_guard<std::mutex> lock(g_log_mu);
+    if (!g_log_on) return;
+    if (name)
+        snprintf(line, sizeof line, fmt, name, d[0], d[1], d[2], d[3], d[4], d[5], log_id(g_log_streams, st));
+    else
+        snprintf(line, sizeof line, fmt, log_id(g_log_streams, st), log_id(g_log_events, ev));
+    g_log_text += line;
+}
+}  // namespace
+void log_launch(const char* kernel, unsigned gx, unsigned gy, unsigned gz, unsigned bx, unsigned by, unsigned bz, hipStream_t st) {
+    const unsigned d[6] = {gx, gy, gz, bx, by, bz};
+    log_line("launch %s grid=(%u,%u,%u) block=(%u,%u,%u) stream=%d\n", kernel, d, st, nullptr);
+}
+void log_record(hipEvent_t ev, hipStream_t st) { log_line("record stream=%d event=%d\n", nullptr, nullptr, st, ev); }
+void log_wait(hipStream_t st, hipEvent_t ev) { log_line("wait stream=%d event=%d\n", nullptr, nullptr, st, ev); }
+
 }  // namespace hipemu
+
+// Switch the log on (and empty it), read it back, switch it off.  hipemu_log_read copies at most cap - 1 characters plus a
+// terminating zero and returns the length of the whole text, so a first call with cap = 0 sizes the buffer.
+extern "C" void hipemu_log_begin() {
+    std::lock_guard<std::mutex> lock(hipemu::g_log_mu);
+    hipemu::g_log_text.clear();
+    hipemu::g_log_streams.assign(1, nullptr);
+    hipemu::g_log_events.clear();
+    hipemu::g_log_on = true;
+}
+extern "C" size_t hipemu_log_read(char* buf, size_t cap) {
+    std::lock_guard<std::mutex> lock(hipemu::g_log_mu);
+    if (buf && cap > 0) {
+        const size_t n = hipemu::g_log_text.size() < cap - 1 ? hipemu::g_log_text.size() : cap - 1;
+        memcpy(buf, hipemu::g_log_text.data(), n);
+        buf[n] = 0;
+    }
+    return hipemu::g_log_text.size();
+}
+extern "C" void hipemu_log_end() {
+    std::lock_guard<std::mutex> lock(hipemu::g_log_mu);
+    hipemu::g_log_on = false;
+}
