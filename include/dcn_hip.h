@@ -564,6 +564,33 @@ int dcn_upsample_backward(const float* gout, int n, int hl, int wl, int ldl, int
                           float* tmp, void* stream);
 size_t dcn_upsample_backward_tmp_bytes(int n, int hl, int w, int d);
 
+/* The same kernels with every optional input and output the engine launches them with (unit tests of the variants no entry point
+ * above reaches); each is the engine's own launcher behind an argument check.
+ * dcn_maxpool_forward_full: bn_stats (nullable, [groups][4][c] as dcn_bn_forward writes them, groups 1 | 2, n % groups == 0): `in` is
+ *   a convolution output and y = relu(in * scale + shift) is applied on the way into the window maximum, per group of n / groups
+ *   images; relu_mask (nullable, with bn_stats only) receives the one-byte-per-float4 sign mask of y, n * hin * win * c / 4 bytes.
+ * dcn_maxpool_backward_full: gout2 (nullable): the gradient of the pooled tensor is gout + gout2. */
+int dcn_maxpool_forward_full(const float* in, const float* bn_stats, int groups, int n, int hin, int win, int c, float* out,
+                             unsigned char* argmax, unsigned char* relu_mask, void* stream);
+int dcn_maxpool_backward_full(const float* gout, const float* gout2, const unsigned char* argmax, int n, int hin, int win, int c,
+                              float* gin, void* stream);
+/* backward of the L2 normalisation fused into dcn_upsample_forward(normalize = 1): gv [n,h,w,d] = gradient w.r.t. the
+ * interpolated map v (re-interpolated from low) given gout = gradient w.r.t. v / ||v|| */
+int dcn_normalize_backward(const float* low, int n, int hl, int wl, int ldl, int d, int h, int w, const float* gout, float* gv,
+                           void* stream);
+/* dcn_upsample_backward with gout_b (nullable, n even): the gradient of images [n / 2, n) as a tensor of its own, and absmax
+ * (nullable): one float, raised to max |glow| */
+int dcn_upsample_backward_full(const float* gout, const float* gout_b, int n, int hl, int wl, int ldl, int d, int h, int w,
+                               float* glow, float* tmp, float* absmax, void* stream);
+/* img [n,3,hw] (NCHW) -> out [n,hw,4] = (R, G, B, 0); absmax (nullable): one float, raised to max |img|, to +inf when img holds a NaN */
+int dcn_image_to_nhwc4(const float* img, int n, int hw, float* out, float* absmax, void* stream);
+/* [rows][3] -> [rows][4] with a zero fourth lane, and back; [rows][d] -> [rows][ld] (ld >= d) with zero pad columns */
+int dcn_pad_c3_to_c4(const float* src, float* dst, int64_t rows, void* stream);
+int dcn_unpad_c4_to_c3(const float* src, float* dst, int64_t rows, void* stream);
+int dcn_pad_rows(const float* src, float* dst, int64_t rows, int d, int ld, void* stream);
+/* out[j] = sum over the rows of m[rows][ld] of column j, j < d <= ld (the fc.bias gradient; fp64 accumulation, fixed order) */
+int dcn_column_sums(const float* m, int64_t rows, int ld, int d, float* out, void* stream);
+
 /* =====================================================================================================
  * 4. Best-match search over a descriptor image (evaluation / heat-map side)
  *

@@ -935,6 +935,13 @@ extern "C" size_t dcn_plan_saved_bytes(const dcn_plan* plan) { return plan ? pla
 extern "C" size_t dcn_plan_workspace_bytes(const dcn_plan* plan) { return plan ? plan->ws_floats * sizeof(float) : 0; }
 extern "C" double dcn_plan_forward_flops(const dcn_plan* plan) { return plan ? plan->flops : 0.0; }
 
+// the fc.bias gradient's launch as a stand-alone call (unit tests): one workgroup per column j < d of m[rows][ld]
+extern "C" int dcn_column_sums(const float* m, int64_t rows, int ld, int d, float* out, void* stream) {
+    if (!m || !out || rows < 1 || d < 1 || ld < d) return DCN_E_INVALID;
+    hipLaunchKernelGGL(colsum_kernel, dim3(d), dim3(1024), 0, (hipStream_t)stream, m, rows, ld, out);
+    return dcn::check_launch();
+}
+
 namespace {
 
 // image_b (optional, grouped plans): the second batch of a forward_pair call -- images [N/2, N) come from there instead of

@@ -1388,3 +1388,61 @@ extern "C" int dcn_maxpool_backward(const float* gout, const unsigned char* argm
     dcn::launch_maxpool_bwd(gout, argmax, gin, n, hin, win, (hin + 2 - 3) / 2 + 1, (win + 2 - 3) / 2 + 1, c, (hipStream_t)stream);
     return dcn::check_launch();
 }
+
+// ---- the same launchers with every optional argument the engine passes them (unit tests of those variants)
+extern "C" int dcn_maxpool_forward_full(const float* in, const float* bn_stats, int groups, int n, int hin, int win, int c,
+                                        float* out, unsigned char* argmax, unsigned char* relu_mask, void* stream) {
+    if (!in || !out || n < 1 || hin < 1 || win < 1 || c < 4 || (c % 4) != 0) return DCN_E_INVALID;
+    if ((groups != 1 && groups != 2) || (n % groups) != 0) return DCN_E_INVALID;
+    if (relu_mask && !bn_stats) return DCN_E_INVALID;
+    dcn::launch_maxpool_fwd(in, out, argmax, n, hin, win, (hin + 2 - 3) / 2 + 1, (win + 2 - 3) / 2 + 1, c, (hipStream_t)stream,
+                            bn_stats, groups, relu_mask);
+    return dcn::check_launch();
+}
+
+extern "C" int dcn_maxpool_backward_full(const float* gout, const float* gout2, const unsigned char* argmax, int n, int hin,
+                                         int win, int c, float* gin, void* stream) {
+    if (!gout || !argmax || !gin || n < 1 || hin < 1 || win < 1 || c < 4 || (c % 4) != 0) return DCN_E_INVALID;
+    dcn::launch_maxpool_bwd(gout, argmax, gin, n, hin, win, (hin + 2 - 3) / 2 + 1, (win + 2 - 3) / 2 + 1, c, (hipStream_t)stream,
+                            gout2);
+    return dcn::check_launch();
+}
+
+extern "C" int dcn_normalize_backward(const float* low, int n, int hl, int wl, int ldl, int d, int h, int w, const float* gout,
+                                      float* gv, void* stream) {
+    if (!low || !gout || !gv || n < 1 || hl < 1 || wl < 1 || d < 1 || ldl < d || h < 1 || w < 1) return DCN_E_INVALID;
+    dcn::launch_normalize_bwd(low, n, hl, wl, ldl, d, h, w, gout, gv, (hipStream_t)stream);
+    return dcn::check_launch();
+}
+
+extern "C" int dcn_upsample_backward_full(const float* gout, const float* gout_b, int n, int hl, int wl, int ldl, int d, int h,
+                                          int w, float* glow, float* tmp, float* absmax, void* stream) {
+    if (!gout || !glow || !tmp || n < 1 || hl < 1 || wl < 1 || d < 1 || ldl < d || h < 1 || w < 1) return DCN_E_INVALID;
+    if (gout_b && (n % 2) != 0) return DCN_E_INVALID;
+    dcn::launch_upsample_bwd(gout, n, hl, wl, ldl, d, h, w, tmp, glow, absmax, (hipStream_t)stream, gout_b);
+    return dcn::check_launch();
+}
+
+extern "C" int dcn_image_to_nhwc4(const float* img, int n, int hw, float* out, float* absmax, void* stream) {
+    if (!img || !out || n < 1 || hw < 1) return DCN_E_INVALID;
+    dcn::launch_nchw3_to_nhwc4(img, out, n, hw, absmax, (hipStream_t)stream);
+    return dcn::check_launch();
+}
+
+extern "C" int dcn_pad_c3_to_c4(const float* src, float* dst, int64_t rows, void* stream) {
+    if (!src || !dst || rows < 1) return DCN_E_INVALID;
+    dcn::launch_pad_c3_to_c4(src, dst, rows, (hipStream_t)stream);
+    return dcn::check_launch();
+}
+
+extern "C" int dcn_unpad_c4_to_c3(const float* src, float* dst, int64_t rows, void* stream) {
+    if (!src || !dst || rows < 1) return DCN_E_INVALID;
+    dcn::launch_unpad_c4_to_c3(src, dst, rows, (hipStream_t)stream);
+    return dcn::check_launch();
+}
+
+extern "C" int dcn_pad_rows(const float* src, float* dst, int64_t rows, int d, int ld, void* stream) {
+    if (!src || !dst || rows < 1 || d < 1 || ld < d) return DCN_E_INVALID;
+    dcn::launch_pad_rows(src, dst, rows, d, ld, (hipStream_t)stream);
+    return dcn::check_launch();
+}

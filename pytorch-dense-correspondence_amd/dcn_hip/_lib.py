@@ -180,6 +180,16 @@ SYMBOLS = {
     "dcn_upsample_backward": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p,
                                       c_void_p]),
     "dcn_upsample_backward_tmp_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
+    "dcn_maxpool_forward_full": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p,
+                                         c_void_p]),
+    "dcn_maxpool_backward_full": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
+    "dcn_normalize_backward": (c_int, [c_void_p] + [c_int] * 7 + [c_void_p, c_void_p, c_void_p]),
+    "dcn_upsample_backward_full": (c_int, [c_void_p, c_void_p] + [c_int] * 7 + [c_void_p] * 4),
+    "dcn_image_to_nhwc4": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    "dcn_pad_c3_to_c4": (c_int, [c_void_p, c_void_p, c_int64, c_void_p]),
+    "dcn_unpad_c4_to_c3": (c_int, [c_void_p, c_void_p, c_int64, c_void_p]),
+    "dcn_pad_rows": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_int, c_void_p]),
+    "dcn_column_sums": (c_int, [c_void_p, c_int64, c_int, c_int, c_void_p, c_void_p]),
     "dcn_split_weights_checked_f16": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                               c_float, c_void_p, c_void_p]),
     "dcn_conv_wgrad_hl_eligible": (c_int, [ctypes.POINTER(ConvDesc)]),

@@ -315,7 +315,10 @@ def test_batch_norm_kernels_vs_torch_cpu(L, rows, C, residual):
 @pytest.mark.parametrize("shape", [(2, 240, 320, 64), (1, 480, 640, 64), (1, 9, 7, 8)], ids=str)
 def test_max_pool_kernels_vs_torch_cpu(L, shape):
     """K2 at the stem's shape (64 channels, 240x320 -> 120x160) and the ResNet50 / 1280x960 one: values, and the backward
-    gather against autograd (ties: random floats have none; the first-maximum rule is covered by the emulator suite)."""
+    gather against autograd.  Random floats have no ties: the first-maximum rule, NaN / -inf windows, every argmax byte and the
+    variants the engine launches (batch norm + ReLU applied on the way in, two cotangents) are held by
+    test_gpu_resample.py / test_emu_resample.py (tests/resample_checks.py: check_maxpool_exact, check_stem_pool_fused,
+    check_stem_chain)."""
     lib = L.get()
     st = L.stream_ptr()
     n, h, w, C = shape
