@@ -609,8 +609,11 @@ int dcn_column_sums(const float* m, int64_t rows, int ld, int d, float* out, voi
  * (row length w):  queries[i] = res_a[uv_a_i], gt_idx[i] = flat index of the ground-truth match in image b.
  *   best_idx / best_dist  [2][q]: argmin / min of d over the image, and of d + (1 - mask) * 1e6 (mask NULL: same as the image)
  *   count                 [2][q]: pixels with d < ||queries[i] - res[gt_idx[i]]|| (image / masked)
- *   dist_sum              [2][q]: sum of the pixel distances of those pixels to the ground-truth pixel
- *   gt_dist               [q]:    that ground-truth descriptor distance */
+ *   dist_sum              [2][q]: sum of the pixel distances of those pixels to the ground-truth pixel: each fp32 distance
+ *                                 rounded to 2^-20 pixel and summed as an integer, so the sum does not depend on the order of
+ *                                 the adds (the same bits from run to run); returned as float((double)sum / 2^20)
+ *   gt_dist               [q]:    that ground-truth descriptor distance
+ *   workspace             dcn_match_statistics_workspace(q) bytes: best keys [2][q] uint64 | distance sums [2][q] uint64 */
 size_t dcn_match_statistics_workspace(int q);
 int dcn_match_statistics(const float* res, int64_t hw, int w, int d, const float* queries, const int64_t* gt_idx, int q,
                          const unsigned char* mask, int64_t* best_idx, float* best_dist, int32_t* count, float* dist_sum,

@@ -17,24 +17,26 @@
 //   pair_search_kernel   grid (pixel chunks, pairs).  A work-item keeps K pixels of res_b[p] in registers (16-byte loads where
 //                        D % 4 == 0), K chosen by D; the pair's query descriptors pass through LDS kQT at a time.  Per query:
 //                        sqrt(sum_k (res_b - d)^2) in fp32 for the K pixels in increasing pixel order with a strict
-//                        comparison (first minimum), ONE wave64 shuffle reduction of the packed key (distance bits << 32 |
-//                        pixel) for the K x 64 pixels, the workgroup's four wavefronts through LDS, then at most one 64-bit
-//                        atomicMin per workgroup and query after a plain load (match_kernels.hip gives the reason).  Integer
-//                        minima only: the result is the same bit for bit from run to run, ties go to the smallest pixel.
+//                        comparison (first minimum), then match_search.h's key and reductions: ONE wavefront reduction for
+//                        the K x 64 pixels, the workgroup's four wavefronts through LDS, at most one commit_min_key per
+//                        workgroup and query.  Integer minima only: the result is the same bit for bit from run to run, ties
+//                        go to the smallest pixel.
 //                        HBM traffic: P * HW * D * 4 bytes of res_b, read once whatever the number of queries.
 //   pair_finish_kernel   one work-item per row: unpacks the key.
 #include "dcn_common.h"
 #include "eval_rows.h"
 #include "hashed_order.h"
+#include "match_search.h"
 
 namespace {
 
 using dcn::align256;
 using dcn::check_offsets_kernel;
+using dcn::kMT;
+using dcn::kMaxD;
 using dcn::order_key;
 using dcn::pair_rows;
 
-constexpr int kMaxD = 64;
 constexpr int kMaxPairs = 1024;
 constexpr int kMaxQ = 1024;
 
@@ -248,7 +250,6 @@ __global__ void __launch_bounds__(kPT) across_pick_kernel(PickArgs a) {
 }
 
 // ------------------------------------------------------------------------------------------------ search
-constexpr int kMT = 256;    // work-items per workgroup
 constexpr int kQT = 64;     // queries staged in LDS at a time
 
 struct SearchArgs {
@@ -318,32 +319,16 @@ __global__ void __launch_bounds__(kMT) pair_search_kernel(SearchArgs a) {
             unsigned bi = (unsigned)pix0;
 #pragma unroll
             for (int k = 0; k < K; ++k) {
-                float d2 = 0.f;
-#pragma unroll
-                for (int c = 0; c < DV; ++c) {
-                    if (c < D) { const float t = v[k][c] - sq[q * DP + c]; d2 = fmaf(t, t, d2); }
-                }
+                const float d2 = dcn::dist2<DT>(v[k], sq + q * DP, D);
                 const float s = pix0 + k * kMT < hw ? sqrtf(d2) : inf;
                 const bool take = s < best;                 // strict, pixels increasing: the first minimum
                 best = take ? s : best;
                 bi = take ? (unsigned)(pix0 + k * kMT) : bi;
             }
-            unsigned long long key = pix0 < hw ? (((unsigned long long)__float_as_uint(best)) << 32) | bi : ~0ull;
-#pragma unroll
-            for (int off = 32; off > 0; off >>= 1) {
-                const unsigned long long o = __shfl_down(key, off, 64);
-                key = o < key ? o : key;
-            }
-            if ((threadIdx.x & 63) == 0) skey[q][threadIdx.x >> 6] = key;
+            dcn::park_key(skey[q], dcn::wave_min_key(pix0 < hw ? dcn::match_key(best, bi) : dcn::kNoKey));
         }
         __syncthreads();
-        if ((int)threadIdx.x < qn) {
-            unsigned long long key = skey[threadIdx.x][0];
-#pragma unroll
-            for (int x = 1; x < kMT / 64; ++x) key = skey[threadIdx.x][x] < key ? skey[threadIdx.x][x] : key;
-            unsigned long long* slot = a.best + lo + q0 + threadIdx.x;
-            if (key != ~0ull && key < __atomic_load_n(slot, __ATOMIC_RELAXED)) atomicMin(slot, key);
-        }
+        if ((int)threadIdx.x < qn) dcn::commit_min_key(a.best + lo + q0 + threadIdx.x, dcn::block_min_key(skey[threadIdx.x]));
     }
 }
 
@@ -354,27 +339,18 @@ __global__ void __launch_bounds__(256) pair_finish_kernel(const unsigned long lo
                                                           int32_t* __restrict__ best_uv, int32_t* __restrict__ row_pair) {
     const int64_t r = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (r >= max_rows) return;
-    int lo = 0, hi = np;
-    while (lo < hi) {                                       // first p with offsets[p + 1] > r
-        const int mid = (lo + hi) >> 1;
-        if (offsets[mid + 1] > r) hi = mid;
-        else lo = mid + 1;
-    }
-    const int p = lo;
-    int bad = 0, n = 0;
-    int64_t first = 0;
-    if (p < np) pair_rows(offsets, offsets_bad, p, max_rows, max_pair_rows, first, n, bad);
-    const bool mine = p < np && r >= first && r < first + n;
-    const unsigned long long k = mine ? best[r] : ~0ull;
-    if (k == ~0ull) {                                       // past the last row, cut off a bad list, or no key written
+    const int p = dcn::row_owner(offsets, np, r);
+    const bool mine = dcn::row_in_pair(offsets, offsets_bad, p, np, r, max_rows, max_pair_rows);
+    const unsigned long long k = mine ? best[r] : dcn::kNoKey;
+    if (k == dcn::kNoKey) {                                 // past the last row, cut off a bad list, or no key written
         norm_diff[r] = __builtin_nanf("");
         best_uv[r] = -1;
         best_uv[max_rows + r] = -1;
         row_pair[r] = -1;
         return;
     }
-    const int i = (int)(unsigned)(k & 0xffffffffull);
-    norm_diff[r] = __uint_as_float((unsigned)(k >> 32));
+    const int i = (int)dcn::key_pixel(k);
+    norm_diff[r] = dcn::key_norm(k);
     best_uv[r] = i % w;
     best_uv[max_rows + r] = i / w;
     row_pair[r] = p;

@@ -17,8 +17,8 @@
 //                       holds one ROW -- its query, ground truth, two keys, two counts, two sums -- and the strip's pixels pass
 //                       by all of them through an LDS tile read at one address by every lane (a broadcast, no bank conflict):
 //                       no shuffle and no barrier in the inner loop, and per row and strip at most one atomic per word.  The
-//                       per-(pixel, row) arithmetic is eval_stats.h's stats_scan's, expression for expression, and every
-//                       accumulation is an integer one, so the two kernels write the same bits.
+//                       per-(pixel, row) arithmetic is the one QueryStats::add (match_search.h) that stats_scan calls, and
+//                       every accumulation is an integer one, so the two kernels write the same bits.
 //   group_rows_kernel   one work-item per row: eval_stats.h's finish_row with the row's own depth and camera row.
 #include "dcn_common.h"
 #include "eval_rows.h"
@@ -30,9 +30,9 @@ namespace {
 using dcn::clip_round;
 using dcn::pair_rows;
 
-constexpr int kMT = dcn::kEvalMT;
+using dcn::kMT;
+using dcn::kMaxD;
 constexpr int kQT = dcn::kEvalQT;
-constexpr int kMaxD = dcn::kEvalMaxD;
 constexpr int kCam = DCN_SAMPLE_CAM_FLOATS;
 
 // float64 products and sums that the compiler may not contract (the rigid inverse, as frame_kernels.hip's camera_row)
@@ -213,11 +213,8 @@ __global__ void __launch_bounds__(kWR) wide_stats_kernel(WideStats b) {
         float t2 = 0.f;                                    // stats_ground_truth's chain
         if constexpr (DT > 0) {
 #pragma unroll
-            for (int k = 0; k < DT; ++k) {
-                q[k] = qs[k];
-                const float t = gt[k] - q[k];
-                t2 = fmaf(t, t, t2);
-            }
+            for (int k = 0; k < DT; ++k) q[k] = qs[k];
+            t2 = dcn::dist2<DT>(q, gt, D);
         } else {
             for (int k = 0; k < D; ++k) {
                 const float qk = qs[k];
@@ -229,8 +226,7 @@ __global__ void __launch_bounds__(kWR) wide_stats_kernel(WideStats b) {
         tt = sqrtf(t2);
         if (blockIdx.x == 0) a.gt_d[r] = tt;               // once per row
     }
-    unsigned long long k0 = ~0ull, k1 = ~0ull, s0 = 0ull, s1 = 0ull;
-    int n0 = 0, n1 = 0;
+    dcn::QueryStats st;
     for (int64_t t0 = p0; t0 < p1; t0 += TP) {
         const int tn = p1 - t0 < TP ? (int)(p1 - t0) : TP;
         __syncthreads();
@@ -239,14 +235,11 @@ __global__ void __launch_bounds__(kWR) wide_stats_kernel(WideStats b) {
         __syncthreads();
         if (!active) continue;
         int pu = (int)(t0 % w), pv = (int)(t0 / w);
-        for (int p = 0; p < tn; ++p) {                     // stats_scan's arithmetic for pixel t0 + p, this work-item's row
+        for (int p = 0; p < tn; ++p) {                     // pixel t0 + p against this work-item's row
+            const bool onm = s_mask[p] != 0;               // (read with the descriptor, not after the square root)
             float d2 = 0.f;
             if constexpr (DT > 0) {
-#pragma unroll
-                for (int k = 0; k < DT; ++k) {
-                    const float t = s_pix[p * DT + k] - q[k];
-                    d2 = fmaf(t, t, d2);
-                }
+                d2 = dcn::dist2<DT>(q, s_pix + p * DT, D);
             } else {
                 for (int k = 0; k < D; ++k) {
                     const float t = s_pix[p * D + k] - s_q[k * kWR + tid];
@@ -254,34 +247,22 @@ __global__ void __launch_bounds__(kWR) wide_stats_kernel(WideStats b) {
                 }
             }
             const float dd = sqrtf(d2);
-            const float dm = s_mask[p] != 0 ? dd : dd + 1e6f;              // masked_norm_diffs
-            const unsigned pix = (unsigned)(t0 + p);
-            const unsigned long long c0k = (((unsigned long long)__float_as_uint(dd)) << 32) | pix;
-            const unsigned long long c1k = (((unsigned long long)__float_as_uint(dm)) << 32) | pix;
-            k0 = c0k < k0 ? c0k : k0;
-            k1 = c1k < k1 ? c1k : k1;
-            const bool c0 = dd < tt, c1 = dm < tt;
-            if (c0 || c1) {
-                const float du = (float)(pu - gu), dv = (float)(pv - gv);
-                const float pd = sqrtf(du * du + dv * dv);
-                const unsigned long long pf = (unsigned long long)((double)pd * dcn::kEvalSumScale + 0.5);
-                if (c0) { ++n0; s0 += pf; }
-                if (c1) { ++n1; s1 += pf; }
-            }
+            if (dd < tt) st.add(true, dd, onm, (unsigned)(t0 + p), tt, pu, pv, gu, gv);
+            else st.offer(true, dd, onm, (unsigned)(t0 + p));              // (few pixels are closer: no float64 step)
             if (++pu == w) { pu = 0; ++pv; }
         }
     }
-    if (active) {                      // stats_scan's filter: almost every key loses against the word's value
+    if (active) {
         const int64_t o0 = r, o1 = a.max_rows + r;
-        if (k0 != ~0ull && k0 < __atomic_load_n(a.best + o0, __ATOMIC_RELAXED)) atomicMin(a.best + o0, k0);
-        if (k1 != ~0ull && k1 < __atomic_load_n(a.best + o1, __ATOMIC_RELAXED)) atomicMin(a.best + o1, k1);
-        if (n0) {
-            atomicAdd(a.count + o0, n0);
-            atomicAdd(a.dist_sum + o0, s0);
+        dcn::commit_min_key(a.best + o0, st.k0);
+        dcn::commit_min_key(a.best + o1, st.k1);
+        if (st.n0) {
+            atomicAdd(a.count + o0, st.n0);
+            atomicAdd(a.dist_sum + o0, st.s0);
         }
-        if (n1) {
-            atomicAdd(a.count + o1, n1);
-            atomicAdd(a.dist_sum + o1, s1);
+        if (st.n1) {
+            atomicAdd(a.count + o1, st.n1);
+            atomicAdd(a.dist_sum + o1, st.s1);
         }
     }
 }
@@ -311,20 +292,11 @@ __global__ void __launch_bounds__(256) group_rows_kernel(GroupRows a) {
     const int64_t r = (int64_t)blockIdx.x * 256 + threadIdx.x;
     const int64_t R = a.out.max_rows;
     if (r >= R) return;
-    int lo = 0, hi = a.ng;
-    while (lo < hi) {                                       // first g with offsets[g + 1] > r
-        const int mid = (lo + hi) >> 1;
-        if (a.offsets[mid + 1] > r) hi = mid;
-        else lo = mid + 1;
-    }
-    const int g = lo;
+    const int g = dcn::row_owner(a.offsets, a.ng, r);
+    const bool mine = dcn::row_in_pair(a.offsets, a.offsets_bad, g, a.ng, r, R, a.max_group_rows) && a.keep[r] != 0;
+    const unsigned long long k0 = mine ? a.best[r] : dcn::kNoKey, k1 = mine ? a.best[R + r] : dcn::kNoKey;
     int bad = 0;
-    int64_t first = 0;
-    int n = 0;
-    if (g < a.ng) pair_rows(a.offsets, a.offsets_bad, g, R, a.max_group_rows, first, n, bad);
-    const bool mine = g < a.ng && r >= first && r < first + n && a.keep[r] != 0;
-    const unsigned long long k0 = mine ? a.best[r] : ~0ull, k1 = mine ? a.best[R + r] : ~0ull;
-    if (!mine || k0 == ~0ull || k1 == ~0ull) {              // past the last row, cut off a bad list, left out, or no key written
+    if (!mine || k0 == dcn::kNoKey || k1 == dcn::kNoKey) {  // past the last row, cut off a bad list, left out, or no key written
         dcn::empty_row(a.out, r);
         return;
     }

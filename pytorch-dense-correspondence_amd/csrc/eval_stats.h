@@ -1,25 +1,22 @@
-// The search and the row finishing of the match statistics, shared by the pair-wise entry (evaluate_kernels.hip: a query's
-// descriptor, depth and camera row come from image a of its pair) and the grouped entry (crossscene_kernels.hip: every row
-// carries its own).  One text for both, so the two entries compute the same bits for the same rows.
+// The search and the row finishing of the match statistics, shared by the single-image entry (match_kernels.hip: queries and
+// flat ground-truth indices as given), the pair-wise entry (evaluate_kernels.hip: a query's descriptor, depth and camera row come
+// from image a of its pair) and the grouped entry (crossscene_kernels.hip: every row carries its own).  One text for all, so
+// the entries compute the same bits for the same rows.  The search primitives (key, reductions, QueryStats) are match_search.h's.
 //
-//   stats_ground_truth / stats_scan   one query tile of a statistics kernel (kEvalMT pixels x up to kEvalQT queries staged in
-//                                     an EvalTile): the fma chain over channels, sqrtf, + 1e6f off the mask, packed-key minima
-//                                     (norm bits << 32 | pixel: ties go to the smallest index, as np.argmin), wave64 shuffle
-//                                     reductions, then per workgroup and query at most one 64-bit atomicMin -- after a plain
-//                                     load: thousands of workgroups target the same few words and almost every key loses.
+//   stats_ground_truth / stats_scan   one query tile of a statistics kernel (kMT pixels x up to kEvalQT queries staged in an
+//                                     EvalTile): per query one QueryStats::add, wavefront reductions, then per workgroup and
+//                                     query at most one commit_min_key and one integer add per count and sum.
 //   finish_row / empty_row            one row of the table from its keys, counts and sums; the depth / 3D half
 //                                     (evaluation.py:1102-1135, :1148-1164) in float64 from the row's fp32 camera row.
-//   stats_workspace_bytes / prepare_stats_scratch   (host) the workspace both entries carve, its fills and the offsets check.
+//   stats_workspace_bytes / prepare_stats_scratch   (host) the workspace both table entries carve, its fills and the offsets check.
 #pragma once
 #include "dcn_common.h"
 #include "eval_rows.h"
+#include "match_search.h"
 
 namespace dcn {
 
-constexpr int kEvalMT = 256;    // work-items (pixels) per workgroup
 constexpr int kEvalQT = 32;     // queries staged in LDS at a time
-constexpr int kEvalMaxD = 64;
-constexpr double kEvalSumScale = 1048576.0;   // pixel distances are summed as integers of 2^-20 pixel: the sum does not depend on the order
 
 // clip_pixel_to_image_size_and_round (evaluation.py:604-607): min(int(round(x)), size - 1), Python 2's round (half away from
 // zero: roundf).  NaN or a negative result reads 0 and sets `bad`.
@@ -38,12 +35,12 @@ __device__ __forceinline__ int clip_round(float x, int size, int& bad) {
 
 // The LDS of one query tile: the kernel declares it __shared__, fills sq / sgu / sgv (and skip), and synchronizes
 struct EvalTile {
-    float sq[kEvalQT * kEvalMaxD];     // query descriptors, [query][D]
+    float sq[kEvalQT * kMaxD];         // query descriptors, [query][D]
     float st[kEvalQT];                 // squared ground-truth distance
     int sgu[kEvalQT], sgv[kEvalQT];    // ground-truth pixel in the searched image
-    unsigned long long skey[2][kEvalQT][kEvalMT / 64];
-    int scnt[2][kEvalQT][kEvalMT / 64];
-    unsigned long long ssum[2][kEvalQT][kEvalMT / 64];
+    unsigned long long skey[2][kEvalQT][kMT / 64];
+    int scnt[2][kEvalQT][kMT / 64];
+    unsigned long long ssum[2][kEvalQT][kMT / 64];
     unsigned char skip[kEvalQT];       // (grouped entry) the row takes no part in the search
 };
 
@@ -68,59 +65,45 @@ __device__ __forceinline__ void stats_ground_truth(EvalTile& s, const float* __r
 // with s.skip set are passed over (uniform per workgroup) and nothing is written for them.  Needs s.st; ends after the
 // atomics, the caller synchronizes before it refills the tile.
 template <int DT, bool SKIP>
-__device__ __forceinline__ void stats_scan(EvalTile& s, const float (&v)[DT > 0 ? DT : kEvalMaxD], int D, int qn, bool in,
+__device__ __forceinline__ void stats_scan(EvalTile& s, const float (&v)[DT > 0 ? DT : kMaxD], int D, int qn, bool in,
                                            bool onm, int64_t pix, int pu, int pv, unsigned long long* best, int32_t* count,
                                            unsigned long long* dist_sum, int64_t max_rows, int64_t row0) {
     const int wv = threadIdx.x >> 6;
     for (int q = 0; q < qn; ++q) {
         if (SKIP && __builtin_amdgcn_readfirstlane((int)s.skip[q])) continue;   // (one scalar branch per query)
-        float d2 = 0.f;
-#pragma unroll
-        for (int k = 0; k < (DT > 0 ? DT : kEvalMaxD); ++k) {
-            if (k < D) { const float t = v[k] - s.sq[q * D + k]; d2 = fmaf(t, t, d2); }
-        }
-        const float dd = sqrtf(d2), tt = sqrtf(s.st[q]);
-        const float dm = onm ? dd : dd + 1e6f;                         // masked_norm_diffs
-        unsigned long long k0 = in ? (((unsigned long long)__float_as_uint(dd)) << 32) | (unsigned)pix : ~0ull;
-        unsigned long long k1 = in ? (((unsigned long long)__float_as_uint(dm)) << 32) | (unsigned)pix : ~0ull;
-        const bool c0 = in && dd < tt, c1 = in && dm < tt;
-        const float du = (float)(pu - s.sgu[q]), dv = (float)(pv - s.sgv[q]);
-        const float pd = sqrtf(du * du + dv * dv);
-        int n0 = c0 ? 1 : 0, n1 = c1 ? 1 : 0;
-        const unsigned long long pf = (unsigned long long)((double)pd * kEvalSumScale + 0.5);
-        unsigned long long s0 = c0 ? pf : 0ull, s1 = c1 ? pf : 0ull;
+        QueryStats t;
+        t.add(in, sqrtf(dist2<DT>(v, s.sq + q * D, D)), onm, (unsigned)pix, sqrtf(s.st[q]), pu, pv, s.sgu[q], s.sgv[q]);
+        // the six reductions of wave_min_key / wave_sum, step by step side by side: six independent shuffles in flight per
+        // step (one after the other they cost group_stats_kernel 6 % at D = 16, profiles/match_search_refactor_bench.json)
 #pragma unroll
         for (int off = 32; off > 0; off >>= 1) {
-            const unsigned long long x = __shfl_down(k0, off, 64), y = __shfl_down(k1, off, 64);
-            k0 = x < k0 ? x : k0;
-            k1 = y < k1 ? y : k1;
-            n0 += __shfl_down(n0, off, 64);
-            n1 += __shfl_down(n1, off, 64);
-            s0 += __shfl_down(s0, off, 64);
-            s1 += __shfl_down(s1, off, 64);
+            const unsigned long long x = __shfl_down(t.k0, off, 64), y = __shfl_down(t.k1, off, 64);
+            t.k0 = x < t.k0 ? x : t.k0;
+            t.k1 = y < t.k1 ? y : t.k1;
+            t.n0 += __shfl_down(t.n0, off, 64);
+            t.n1 += __shfl_down(t.n1, off, 64);
+            t.s0 += __shfl_down(t.s0, off, 64);
+            t.s1 += __shfl_down(t.s1, off, 64);
         }
         if ((threadIdx.x & 63) == 0) {
-            s.skey[0][q][wv] = k0; s.skey[1][q][wv] = k1;
-            s.scnt[0][q][wv] = n0; s.scnt[1][q][wv] = n1;
-            s.ssum[0][q][wv] = s0; s.ssum[1][q][wv] = s1;
+            s.skey[0][q][wv] = t.k0; s.skey[1][q][wv] = t.k1;
+            s.scnt[0][q][wv] = t.n0; s.scnt[1][q][wv] = t.n1;
+            s.ssum[0][q][wv] = t.s0; s.ssum[1][q][wv] = t.s1;
         }
     }
     __syncthreads();
     if ((int)threadIdx.x < 2 * qn) {
         const int which = threadIdx.x / qn, q = threadIdx.x - which * qn;
         if (!(SKIP && s.skip[q])) {
-            unsigned long long key = s.skey[which][q][0];
             int n = s.scnt[which][q][0];
             unsigned long long sum = s.ssum[which][q][0];
 #pragma unroll
-            for (int x = 1; x < kEvalMT / 64; ++x) {
-                key = s.skey[which][q][x] < key ? s.skey[which][q][x] : key;
+            for (int x = 1; x < kMT / 64; ++x) {
                 n += s.scnt[which][q][x];
                 sum += s.ssum[which][q][x];
             }
             const int64_t o = (int64_t)which * max_rows + row0 + q;
-            unsigned long long* slot = best + o;
-            if (key != ~0ull && key < __atomic_load_n(slot, __ATOMIC_RELAXED)) atomicMin(slot, key);
+            commit_min_key(best + o, block_min_key(s.skey[which][q]));
             if (n) {
                 atomicAdd(count + o, n);
                 atomicAdd(dist_sum + o, sum);
@@ -183,7 +166,7 @@ __device__ __forceinline__ void finish_row(const EvalRowOut& o, int64_t r, int p
                                            unsigned long long s1, int nm, int64_t hw, int w) {
     const int64_t R = o.max_rows;
     const double nan = __builtin_nan("");
-    const int i0 = (int)(unsigned)(k0 & 0xffffffffull), i1 = (int)(unsigned)(k1 & 0xffffffffull);
+    const int i0 = (int)key_pixel(k0), i1 = (int)key_pixel(k1);
     const int u0 = i0 % w, v0 = i0 / w, u1 = i1 % w, v1 = i1 / w;
     o.row_pair[r] = p;
     o.pred_uv[r] = u0;
@@ -191,8 +174,8 @@ __device__ __forceinline__ void finish_row(const EvalRowOut& o, int64_t r, int p
     o.pred_uv[2 * R + r] = u1;
     o.pred_uv[3 * R + r] = v1;
     o.col[(int64_t)DCN_EVAL_COL_NORM_DIFF_DESCRIPTOR_GROUND_TRUTH * R + r] = (double)gt_d;
-    o.col[(int64_t)DCN_EVAL_COL_NORM_DIFF_DESCRIPTOR * R + r] = (double)__uint_as_float((unsigned)(k0 >> 32));
-    o.col[(int64_t)DCN_EVAL_COL_NORM_DIFF_DESCRIPTOR_MASKED * R + r] = (double)__uint_as_float((unsigned)(k1 >> 32));
+    o.col[(int64_t)DCN_EVAL_COL_NORM_DIFF_DESCRIPTOR * R + r] = (double)key_norm(k0);
+    o.col[(int64_t)DCN_EVAL_COL_NORM_DIFF_DESCRIPTOR_MASKED * R + r] = (double)key_norm(k1);
     {
         const double du = (double)(gu - u0), dv = (double)(gv - v0), dum = (double)(gu - u1), dvm = (double)(gv - v1);
         o.col[(int64_t)DCN_EVAL_COL_PIXEL_MATCH_ERROR_L2 * R + r] = sqrt(du * du + dv * dv);

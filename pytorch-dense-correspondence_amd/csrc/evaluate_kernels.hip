@@ -4,10 +4,8 @@
 //
 //   pair_stats_kernel   grid (pixel tiles, pairs).  match_stats_kernel's scheme (match_kernels.hip) per pair: one work-item per
 //                       pixel of res_b[p] with its descriptor in registers, the queries of THAT pair staged in LDS (their
-//                       descriptors gathered from res_a[p] here), packed-key min (norm bits << 32 | pixel: ties go to the
-//                       smallest index, as np.argmin), wave64 shuffle reductions, then per workgroup and query at most one
-//                       64-bit atomicMin -- after a plain load, for the reason given there: thousands of workgroups target the
-//                       same few words and almost every key loses.  Also counts the pair's non-zero mask pixels.
+//                       descriptors gathered from res_a[p] here), then match_search.h's keys and reductions.  Also counts the
+//                       pair's non-zero mask pixels.
 //                       HBM traffic: P * HW * D * 4 bytes of res_b once, plus P * HW mask bytes; with at most a few dozen
 //                       queries per pair a launch per pair would be mostly launch and drain.
 //   pair_rows_kernel    one work-item per row: unpacks the keys and finishes the columns; the depth / 3D half (:1102-1135,
@@ -22,9 +20,9 @@ namespace {
 using dcn::clip_round;
 using dcn::pair_rows;
 
-constexpr int kMT = dcn::kEvalMT;
+using dcn::kMT;
+using dcn::kMaxD;
 constexpr int kQT = dcn::kEvalQT;
-constexpr int kMaxD = dcn::kEvalMaxD;
 constexpr int kCam = DCN_SAMPLE_CAM_FLOATS;
 
 struct PairStats {
@@ -125,21 +123,11 @@ __global__ void __launch_bounds__(256) pair_rows_kernel(PairRows a) {
     const int64_t r = (int64_t)blockIdx.x * 256 + threadIdx.x;
     const int64_t R = a.out.max_rows;
     if (r >= R) return;
-    // the pair of row r: the last p with offsets[p] <= r among the pairs that have rows
-    int lo = 0, hi = a.np;
-    while (lo < hi) {                                       // first p with offsets[p + 1] > r
-        const int mid = (lo + hi) >> 1;
-        if (a.offsets[mid + 1] > r) hi = mid;
-        else lo = mid + 1;
-    }
-    const int p = lo;
+    const int p = dcn::row_owner(a.offsets, a.np, r);
+    const bool mine = dcn::row_in_pair(a.offsets, a.offsets_bad, p, a.np, r, R, a.max_pair_rows);
+    const unsigned long long k0 = mine ? a.best[r] : dcn::kNoKey, k1 = mine ? a.best[R + r] : dcn::kNoKey;
     int bad = 0;
-    int64_t first = 0;
-    int n = 0;
-    if (p < a.np) pair_rows(a.offsets, a.offsets_bad, p, R, a.max_pair_rows, first, n, bad);
-    const bool mine = p < a.np && r >= first && r < first + n;
-    const unsigned long long k0 = mine ? a.best[r] : ~0ull, k1 = mine ? a.best[R + r] : ~0ull;
-    if (!mine || k0 == ~0ull || k1 == ~0ull) {              // past the last row, cut off a bad list, or no key written
+    if (!mine || k0 == dcn::kNoKey || k1 == dcn::kNoKey) {  // past the last row, cut off a bad list, or no key written
         dcn::empty_row(a.out, r);
         return;
     }

@@ -36,7 +36,8 @@ def match_statistics(res_b, queries, gt_idx, mask=None):
     (u + W*v) of the ground-truth match in image b, mask: optional [H, W] (non-zero = on the object).
     One pass over res_b (evaluation.py:1046-1100 for every query) -> dict of device tensors, "image" / "masked" pairs as
     [2, Q]: best_idx, best_dist, count (pixels closer than the ground truth), dist_sum (their pixel distance to it), and
-    gt_dist [Q].  Without a mask the "masked" row of each is a copy of the "image" row, bit for bit."""
+    gt_dist [Q].  dist_sum is an integer sum of the distances rounded to 2^-20 pixel: the same bits from
+    run to run.  Without a mask the "masked" row of each equals the "image" row, bit for bit."""
     lib = _lib.get()
     h, w, d = (int(s) for s in res_b.shape)
     res2 = res_b.reshape(-1, d).contiguous().float()

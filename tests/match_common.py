@@ -214,10 +214,15 @@ def stats_reference(nd, gt, mask, w):
                  (pd * closer_m).sum(1), pd)
 
 
-def fixed_point_average(pd, closer):
-    """evaluate_kernels.hip's column: the fp32 pixel distances rounded to 2^-20 pixel, summed as integers, over the count"""
+def fixed_point_sum(pd, closer):
+    """The kernels' sum of pixel distances: the fp32 distances rounded to 2^-20 pixel, summed as integers (int64 per query)"""
     pf = np.floor(np.sqrt((pd ** 2).astype(F32)).astype(F64) * 1048576.0 + 0.5).astype(np.int64)
-    total, n = (pf * closer).sum(1), closer.sum(1)
+    return (pf * closer).sum(1)
+
+
+def fixed_point_average(pd, closer):
+    """evaluate_kernels.hip's column: that sum over the count"""
+    total, n = fixed_point_sum(pd, closer), closer.sum(1)
     return np.where(n > 0, total.astype(F64) / 1048576.0 / np.maximum(n, 1), 0.0)
 
 
@@ -285,14 +290,20 @@ def check_match_statistics(case, device):
     h, w, _ = case.res.shape
     res, q, g = _t(case.res, device), _t(r.queries[:Q], device), _t(gt, device)
     for mask in (case.mask, None):
-        s = stats_reference(nd, gt, case.mask if mask is not None else np.ones((h, w), np.uint8), w)
+        s_mask = case.mask if mask is not None else np.ones((h, w), np.uint8)
+        s = stats_reference(nd, gt, s_mask, w)
         out = {k: v.cpu().numpy() for k, v in match.match_statistics(res, q, g, None if mask is None else _t(mask, device)).items()}
         _assert_stats((out["best_idx"], out["best_dist"], out["count"], out["gt_dist"]), s, nd, case.name)
+        with np.errstate(invalid="ignore"):
+            md = nd.astype(F64) + (1.0 - (s_mask.reshape(-1) != 0))[None, :] * 1e6
+        closer = (nd < s.gt_dist[:, None], md < s.gt_dist[:, None].astype(F64))
         for half, (n, want) in enumerate(((s.count, s.sum), (s.count_m, s.sum_m))):
             assert (np.abs(out["dist_sum"][half] - want) <= n * 2.0 ** -20 * want).all(), (case.name, half)
+            total = fixed_point_sum(s.pixel_dist, closer[half])          # the integer sum, returned as float32(sum / 2^20)
+            assert np.array_equal(bits(out["dist_sum"][half]), bits((total.astype(F64) / 1048576.0).astype(F32))), (case.name, half)
         if Q > 2:                                            # the ground truth is the best pixel: nothing is closer
             assert out["count"][0][2] == 0 and out["dist_sum"][0][2] == 0.0
-        if mask is None:                                     # both halves equal, the float-atomic sums bit for bit
+        if mask is None:                                     # both halves equal, the integer sums' float32 bit for bit
             for k in ("best_idx", "best_dist", "count"):
                 assert np.array_equal(out[k][0], out[k][1]), (case.name, k)
             assert np.array_equal(bits(out["dist_sum"][0]), bits(out["dist_sum"][1])), case.name
@@ -407,7 +418,7 @@ def check_four_entry_points_agree(case, device):
 
 
 def check_run_to_run(case, device):
-    """Two consecutive calls of each entry point: identical indices and norm bits"""
+    """Two consecutive calls of each entry point: identical indices, norm bits and distance sums"""
     from dcn_hip import evaluate, match
     r = reference(case)
     Q = case.q1
@@ -419,7 +430,7 @@ def check_run_to_run(case, device):
         s = match.match_statistics(res, q, g, mask)
         m = evaluate.best_match_pairs(_t(b.res_b, device), _t(b.queries, device), _t(b.offsets, device))
         t = _pair_statistics(case, device)[1]
-        return [idx, dist, nd, s["best_idx"], s["best_dist"], s["count"], s["gt_dist"], m.best_uv,
+        return [idx, dist, nd, s["best_idx"], s["best_dist"], s["count"], s["dist_sum"], s["gt_dist"], m.best_uv,
                 m.norm_diff_descriptor_best_match, t.pred_uv, t.closer, t.column("norm_diff_descriptor"),
                 t.column("norm_diff_descriptor_masked"), t.column("average_l2_distance_for_false_positives")]
     for x, y in zip(calls(), calls()):
