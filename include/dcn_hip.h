@@ -1321,6 +1321,57 @@ int dcn_heat_maps(int p, int h, int w, int d, const float* res_b, const float* q
                   int64_t max_rows, float variance, const uint8_t* colour_table, uint8_t* out, int32_t* status,
                   void* workspace, void* stream);
 
+/* =====================================================================================================
+ * 16. Rendering depth images and foreground masks from scene meshes -- the output of the reference's data collection
+ *     (modules/dense_correspondence_manipulation/change_detection/change_detection.py: ChangeDetection.run and
+ *     render_depth_images draw the fused mesh from every logged camera pose through director / VTK / OpenGL windows) as a
+ *     z-buffer rasteriser.  The mask rules are the reference's; the rasteriser has no reference text and is DEFINED here:
+ *     every step is an integer operation or one correctly rounded float64 operation (no fma), so the image is the same bit
+ *     for bit from run to run and equal to a numpy statement of these rules (tests/render_common.py).
+ *
+ * 16a. dcn_render_depth.  vertices float [v][3] in the world frame, triangles int32 [t][3] (an index outside [0, v) draws
+ *     nothing), camera_to_world float [f][16] row-major, the pose convention of sections 5 and 10 (camera frame: x right, y
+ *     down, z forward), the pinhole (fx, fy, cx, cy), h x w pixels (1 .. 16384 each), 0 < z_near < 65.536 (metres).
+ *       (a) world-to-camera is the rigid inverse of the pose in float64: rows (R^T | -R^T t) with
+ *           (R^T t)_i = (p[i] * p[3] + p[4 + i] * p[7]) + p[8 + i] * p[11], p the pose's entries widened to float64
+ *       (b) a vertex in the camera frame: ((a0 * x + a1 * y) + a2 * z) + a3 per row
+ *       (c) a triangle with a vertex that is NOT at z >= z_near (behind the camera, too close, NaN) is dropped whole and
+ *           counted in status[frame][0].  Nothing is clipped: OpenGL would clip such a triangle against its near plane and
+ *           draw the rest.
+ *       (d) u = (fx * x) / z + cx, v = (fy * y) / z + cy, snapped to 1/256 pixel: X = rint(u * 256), ties to even.  A
+ *           triangle with a snapped coordinate outside +-2^30 (2^22 pixels; NaN, infinity) is dropped whole and counted in
+ *           status[frame][1].
+ *       (e) pixel (px, py) is covered when its centre (256 px + 128, 256 py + 128) is inside by the three int64 edge
+ *           functions E(a -> b, c) = (bx - ax) * (cy - ay) - (by - ay) * (cx - ax): E0 of v1 -> v2, E1 of v2 -> v0, E2 of
+ *           v0 -> v1.  A triangle with E0 + E1 + E2 < 0 has v1 and v2 exchanged first (both windings draw); one with
+ *           E0 + E1 + E2 == 0 is skipped.  Top-left rule: a centre with E == 0 belongs to the triangle when the edge a -> b has
+ *           by < ay (a left edge) or by == ay and bx > ax (a top edge).
+ *       (f) z = (E0 + E1 + E2) / ((E0 / z0 + E1 / z1) + E2 / z2) in float64, the integers converted to float64 first (ties to
+ *           even), z_i the camera-frame depth of v_i; when z0 == z1 == z2 (a triangle facing the camera) z is that value,
+ *           so that such a plane shows its own millimetres and not, after two roundings, one less.  (The quotient form is
+ *           used, and not 1 / (...) * (E0 + E1 + E2): it has one rounding fewer and is exact at power-of-two depths.)
+ *       (g) mm = trunc(z * 1000), as vtkImageShiftScale fills an unsigned short with scale 1000.  A fragment with mm == 0 or
+ *           mm >= 65536 leaves the pixel as it is (alone on its pixel: 0).
+ *       (h) the pixel keeps the minimum mm over the triangles that cover it (an unsigned atomicMin: no order dependence).
+ *       depth uint16 [f][h][w] millimetres, 0: no surface.  status int32 [f][2]: triangles dropped by (c) and by (d).
+ *     A triangle is walked by one work-item unless its bounding box, clipped to the image, holds more than large_threshold
+ *     pixels (< 0: the default, 1024); those are drawn tile by tile by whole workgroups.  The image does not depend on it.
+ *     Several frames per launch (as many as 64 MiB of per-frame triangle lists hold, at most 64); fills are kernels; no host
+ *     synchronisation.  v >= 0, 0 <= t < 2^31 (t == 0: all zeros), f >= 1.
+ * 16b. dcn_render_masks on n pixels (any number of images): with depth_b, computeForegroundMask's preparation and
+ *     computeForegroundMaskFromDepthImagePair (:219-272, :314-329): int32, zeros read as INT32_MAX,
+ *     mask = (b - f) > threshold, depth_change = mask * f; with depth_b == NULL computeForegroundMaskUsingCropStrategy
+ *     (:274-312): mask = f > 0, depth_change = f.  mask uint8 0 / 1, visible (or NULL) = mask * 255 (the "visible" mask of
+ *     ChangeDetection.run), depth_change (or NULL) uint16.  threshold >= 0.  Pointers as an allocator returns them (8-byte
+ *     aligned): whole dwords are stored, the last n % 4 pixels singly.
+ * ===================================================================================================== */
+size_t dcn_render_depth_workspace(int v, int64_t t, int f, int h, int w);
+int dcn_render_depth(int v, int64_t t, int f, int h, int w, const float* vertices, const int32_t* triangles,
+                     const float* camera_to_world, double fx, double fy, double cx, double cy, double z_near,
+                     int large_threshold, uint16_t* depth, int32_t* status, void* workspace, void* stream);
+int dcn_render_masks(int64_t n, const uint16_t* depth_f, const uint16_t* depth_b, int threshold, uint8_t* mask,
+                     uint8_t* visible, uint16_t* depth_change, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

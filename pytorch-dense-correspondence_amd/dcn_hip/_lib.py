@@ -267,6 +267,10 @@ SYMBOLS = {
     "dcn_descriptor_normalize": (c_int, [c_int, c_int, c_int, c_int] + [c_void_p] * 6 + [ctypes.POINTER(PictureFamily * 2),
                                                                                         c_void_p]),
     "dcn_heat_maps": (c_int, [c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int64, c_float] + [c_void_p] * 5),
+    "dcn_render_depth_workspace": (c_size_t, [c_int, c_int64, c_int, c_int, c_int]),
+    "dcn_render_depth": (c_int, [c_int, c_int64, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p] + [ctypes.c_double] * 5
+                         + [c_int] + [c_void_p] * 4),
+    "dcn_render_masks": (c_int, [c_int64, c_void_p, c_void_p, c_int] + [c_void_p] * 4),
 }
 
 ERRORS = {-1: "DCN_E_INVALID (bad argument)", -2: "DCN_E_LAUNCH (kernel launch failed)",
