@@ -1372,6 +1372,78 @@ int dcn_render_depth(int v, int64_t t, int f, int h, int w, const float* vertice
 int dcn_render_masks(int64_t n, const uint16_t* depth_f, const uint16_t* depth_b, int threshold, uint8_t* mask,
                      uint8_t* visible, uint16_t* depth_change, void* stream);
 
+/* =====================================================================================================
+ * 17. From logged sensor depth images and camera poses to the scene's meshes: TSDF fusion, surface extraction and the box
+ *     crop -- what the reference's data processing gets from its collaborators (spartan's extract_and_fuse_single_scene.py
+ *     runs a CUDA tsdf-fusion binary and marching cubes, doc/data_processing_single_scene.md:42-57; director's cropToBox makes
+ *     the foreground mesh, fusion_reconstruction.py:246-258, 316-332).  Neither has reference text in the checkout, so the
+ *     arithmetic is DEFINED here in the style of section 16: every step is an integer operation or one correctly rounded
+ *     float64 operation (no fma); results are the same bit for bit from run to run and equal to a numpy statement of these
+ *     rules (tests/fusion_common.py).  Pose convention, rigid inverse and camera-frame point: rules 16(a) and 16(b).
+ *
+ * 17a. dcn_tsdf_integrate.  The volume: nx, ny, nz voxels (1 .. 1024 each, x fastest: voxel (i, j, k) at (k * ny + j) * nx + i),
+ *     origin double [3] (a HOST pointer) and voxel_size s > 0 in metres, trunc_margin mu > 0.  Its state: sum int32 [n] and
+ *     weight int32 [n], zero for an empty volume (the caller fills them, e.g. with dcn_fill_bytes); status int32 [1], ADDED to.
+ *     depth uint16 [f][h][w] millimetres (h, w in 1 .. 16384), camera_to_world float [f][16], the pinhole (fx, fy, cx, cy),
+ *     pixel_offset o, 0 <= max_depth_mm <= 65535.  Per voxel, for the frames in the order given:
+ *       1. world centre: origin_x + s * i (one product, one sum), likewise y and z
+ *       2. the camera-frame point (x, y, z) by 16(a), 16(b)
+ *       3. the frame is skipped unless z > 0 (NaN skips)
+ *       4. u = (fx * x) / z + cx, v = (fy * y) / z + cy as 16(d) orders them; px = floor(u + o), py = floor(v + o); skipped
+ *          unless 0 <= px < w and 0 <= py < h (NaN and infinity skip)
+ *       5. o = 0.5 reads integer pixel coordinates as pixel CENTRES -- the sensor's convention and tsdf-fusion's roundf.
+ *          o = 0 is for images made by dcn_render_depth, whose pixel px has its centre at px + 0.5 (rule 16(e)): there the
+ *          pixel that holds the projection is floor(u).
+ *       6. mm = depth[py][px]; skipped when mm == 0 or mm > max_depth_mm
+ *       7. d = mm / 1000.0, diff = d - z; skipped unless diff > -mu
+ *       8. t = min(1.0, diff / mu), q = (int) rint(t * 32768.0), ties to even
+ *       9. a voxel whose weight is >= 65535 takes no further frame: the frame is counted in status[0] instead (so
+ *          |sum| < 2^31)
+ *      10. otherwise sum += q, weight += 1
+ *     The sums are integers: the result does not depend on how the frames are split over launches (frames_per_launch, 1 .. 64,
+ *     < 0: the default 32) or over calls -- calls accumulate.  Frames are walked in order, which settles rule 9.  The signed
+ *     distance of a voxel is sum / weight / 32768 * mu.  One work-item per voxel; no host synchronisation.
+ * 17b. dcn_tsdf_extract: the zero level of sum / weight by MARCHING TETRAHEDRA on the Kuhn split (not marching cubes: some
+ *     twice the triangles, no ambiguous cases, watertight).  A voxel is inside when sum < 0, outside otherwise.
+ *       Cube (i, j, k) has its corners c = bx + 2 by + 4 bz at (i + bx, j + by, k + bz); it is valid when all eight have
+ *       weight >= min_weight (>= 1).  A valid cube is split into six tetrahedra, one per permutation (a, b, c) of the axes in
+ *       lexicographic order (x < y < z): vertices corner 0, e_a, e_a + e_b, corner 7 in this order.  Every tetrahedron edge
+ *       runs from its lower voxel A in one of 7 directions x, y, z, xy, xz, yz, xyz (ids 0 .. 6).
+ *       Vertices: an edge from A to B carries one vertex when its ends are on different sides and a valid cube has both ends
+ *       among its corners.  fa = (double) sumA / (double) weightA, fb likewise, t = fa / (fa - fb); grid coordinate
+ *       (double) iA + t on each axis the direction moves along, (double) iA on the others; world = origin + s * g (a product,
+ *       then a sum), rounded once to float.  Vertex ids ascend by (voxel index, direction id).
+ *       Triangles, per tetrahedron by its inside vertices in vertex order, e(p, q) the vertex of the edge between p and q:
+ *       one inside p, outside q1 q2 q3: (e(p,q1), e(p,q2), e(p,q3)); two inside p1 p2, outside q1 q2: the quad e(p1,q1),
+ *       e(p1,q2), e(p2,q2), e(p2,q1) as triangles (0, 1, 2) and (0, 2, 3); three inside p1 p2 p3, outside q: (e(p1,q),
+ *       e(p2,q), e(p3,q)).  The last two vertices of a triangle are exchanged where needed so that its normal points to the
+ *       outside (decided on the unit cube with every t = 1/2; the level set in a tetrahedron is planar, so it holds for every
+ *       t).  Triangles ascend by (cube index, tetrahedron id, triangle 0 / 1).
+ *     vertices float [max_vertices][3], triangles int32 [max_triangles][3] (unused rows -1), counts int32 [2]: the TRUE numbers
+ *     of vertices and triangles (capped at INT32_MAX) even where they exceed the capacities.  Rows beyond a capacity are not
+ *     written; a triangle that names an unwritten vertex is a row of -1 (dcn_render_depth draws nothing for it).  The order
+ *     comes from exclusive scans over per-voxel counts (reduce per workgroup, one workgroup over the totals, apply).
+ * 17c. dcn_mesh_crop: director_utils.py cropToBox / cropToLineSegment (:151-178).  segments double [3][7] (a HOST pointer),
+ *     per axis of the box frame what those lines compute in numpy float64: point1 [3], axis' [3], length'.  A point's scalar is
+ *     ((d0 * a0 + d1 * a1) + d2 * a2), d = p - point1, a = axis' -- director's labelPointDistanceAlongAxis, which is not in
+ *     the checkout: the dot product, stated here.  A triangle survives an axis when all three of its points have the scalar
+ *     in [0, length'], bounds included (thresholdCells on a point array: vtkThreshold's all-scalars rule), and the crop when
+ *     it survives the three axes.  A row naming an index outside [0, v) does not survive.  Surviving triangles keep their
+ *     order; the vertices they use keep theirs and are renumbered (VTK's point order after vtkThreshold is not reproduced).
+ *     Capacities, counts and -1 rows as in 17b.  0 <= t < 2^31.
+ * ===================================================================================================== */
+int dcn_tsdf_integrate(int nx, int ny, int nz, const double* origin, double voxel_size, double trunc_margin, int f, int h, int w,
+                       const uint16_t* depth, const float* camera_to_world, double fx, double fy, double cx, double cy,
+                       double pixel_offset, int max_depth_mm, int frames_per_launch, int32_t* sum, int32_t* weight,
+                       int32_t* status, void* stream);
+size_t dcn_tsdf_extract_workspace(int nx, int ny, int nz);
+int dcn_tsdf_extract(int nx, int ny, int nz, const double* origin, double voxel_size, const int32_t* sum, const int32_t* weight,
+                     int min_weight, int max_vertices, int max_triangles, float* vertices, int32_t* triangles, int32_t* counts,
+                     void* workspace, void* stream);
+size_t dcn_mesh_crop_workspace(int v, int64_t t);
+int dcn_mesh_crop(int v, int64_t t, const float* vertices, const int32_t* triangles, const double* segments, int max_vertices,
+                  int max_triangles, float* out_vertices, int32_t* out_triangles, int32_t* counts, void* workspace, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -271,6 +271,13 @@ SYMBOLS = {
     "dcn_render_depth": (c_int, [c_int, c_int64, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p] + [ctypes.c_double] * 5
                          + [c_int] + [c_void_p] * 4),
     "dcn_render_masks": (c_int, [c_int64, c_void_p, c_void_p, c_int] + [c_void_p] * 4),
+    "dcn_tsdf_integrate": (c_int, [c_int, c_int, c_int, c_void_p, ctypes.c_double, ctypes.c_double, c_int, c_int, c_int,
+                                   c_void_p, c_void_p] + [ctypes.c_double] * 5 + [c_int, c_int] + [c_void_p] * 4),
+    "dcn_tsdf_extract_workspace": (c_size_t, [c_int, c_int, c_int]),
+    "dcn_tsdf_extract": (c_int, [c_int, c_int, c_int, c_void_p, ctypes.c_double, c_void_p, c_void_p, c_int, c_int, c_int]
+                         + [c_void_p] * 5),
+    "dcn_mesh_crop_workspace": (c_size_t, [c_int, c_int64]),
+    "dcn_mesh_crop": (c_int, [c_int, c_int64, c_void_p, c_void_p, c_void_p, c_int, c_int] + [c_void_p] * 5),
 }
 
 ERRORS = {-1: "DCN_E_INVALID (bad argument)", -2: "DCN_E_LAUNCH (kernel launch failed)",

@@ -8,8 +8,8 @@ of a scene's meshes from its logged camera poses -- what the reference's data co
     write_scene_images(processed_dir, frame_ids, im)             # the reference's four files per frame, one copy
 
 The rasteriser's arithmetic is defined in the header (rules (a)-(h)); it is not OpenGL's: a triangle that reaches in front of
-``z_near`` is dropped whole, not clipped, and counted in ``status``.  TSDF fusion, mesh cropping and the director applications
-of the reference are not provided: the meshes come from files."""
+``z_near`` is dropped whole, not clipped, and counted in ``status``.  The meshes come from files or from ``dcn_hip.fusion``
+(TSDF fusion, surface extraction, box crop); the director applications of the reference are not provided."""
 import collections
 import os
 
@@ -141,6 +141,26 @@ def read_ply(path):
     return np.ascontiguousarray(vertices), np.ascontiguousarray(tris.astype(np.int32))
 
 
+def write_ply(path, vertices, triangles):
+    """Writes a binary little-endian PLY file read_ply reads back as it is: float x, y, z and ``uchar int`` face lists.
+    Triangle rows that hold a negative index (the padding of dcn_hip.fusion's untrimmed meshes) are left out.  -> path"""
+    v = np.ascontiguousarray(np.asarray(vertices, dtype="<f4").reshape(-1, 3))
+    t = np.asarray(triangles, dtype=np.int64).reshape(-1, 3)
+    t = t[(t >= 0).all(axis=1)]
+    if t.size and t.max() >= len(v):
+        raise ValueError("a triangle names a vertex outside 0 .. %d" % (len(v) - 1))
+    faces = np.zeros(len(t), dtype=[("_count", "u1"), ("_index", "<i4", (3,))])
+    faces["_count"] = 3
+    faces["_index"] = t
+    head = ["ply", "format binary_little_endian 1.0", "element vertex %d" % len(v), "property float x", "property float y",
+            "property float z", "element face %d" % len(t), "property list uchar int vertex_indices", "end_header"]
+    with open(path, "wb") as f:
+        f.write(("\n".join(head) + "\n").encode("ascii"))
+        f.write(v.tobytes())
+        f.write(faces.tobytes())
+    return path
+
+
 class Mesh(object):
     """vertices float32 [V, 3] in the world frame and triangles int32 [T, 3] on one device.  Built from host arrays or tensors
     (checked: shapes, every index inside [0, V)); ``device`` defaults to the current GPU (the CPU under the test-only
@@ -166,6 +186,10 @@ class Mesh(object):
     @classmethod
     def from_ply(cls, path, device=None):
         return cls(*read_ply(path), device=device)
+
+    def to_ply(self, path):
+        """One copy to the host and ``write_ply``: the reference's fusion_mesh.ply / fusion_mesh_foreground.ply.  -> path"""
+        return write_ply(path, self.vertices.cpu().numpy(), self.triangles.cpu().numpy())
 
     @property
     def device(self):
