@@ -1444,6 +1444,56 @@ size_t dcn_mesh_crop_workspace(int v, int64_t t);
 int dcn_mesh_crop(int v, int64_t t, const float* vertices, const int32_t* triangles, const double* segments, int max_vertices,
                   int max_triangles, float* out_vertices, int32_t* out_triangles, int32_t* counts, void* workspace, void* stream);
 
+/* =====================================================================================================
+ * 18. Painting mesh vertices from their views: colour fusion (what spartan's tsdf-fusion writes into fusion_mesh.ply as a colour
+ *     per vertex) and the descriptor-coloured mesh (mesh_descriptor_color_app.py: DescriptorMeshColor.color_mesh_using_descriptors;
+ *     MeshColorizer in change_detection/mesh_processing.py) as ONE operation.  Both classes live in mesh_processing.mesh_render,
+ *     which is not in the checkout, so as in sections 16 and 17 the arithmetic is DEFINED here: every step is an integer operation
+ *     or one correctly rounded float64 operation (no fma); results are the same bit for bit from run to run and equal to a numpy
+ *     statement of these rules (tests/paint_common.py).  Pose convention, rigid inverse and camera-frame point: rules 16(a) and
+ *     16(b); the projection: rule 17a.4 (one text in the library for all three, used by sections 17 and 18).
+ *
+ * 18a. dcn_mesh_paint accumulates f views into per-vertex state; calls accumulate.  vertices float [v][3] in the world frame;
+ *     valid_vertices: a device int32 [1] or NULL -- rows at or beyond it (a negative value: every row) take nothing, which is how
+ *     an untrimmed mesh of section 17 passes counts[0:1] without a read-back.  images [f][h][w][c] of image_type DCN_PAINT_UINT8
+ *     (the store's RGB layout) or DCN_PAINT_FLOAT (the evaluation's descriptor layout), 1 <= c <= 32; depth uint16 [f][h][w]
+ *     millimetres; mask uint8 [f][h][w] or NULL; camera_to_world float [f][16]; the pinhole (fx, fy, cx, cy); pixel_offset o;
+ *     margin_mm >= 0.  The state, zero when empty (the caller fills it, e.g. with dcn_fill_bytes): count int32 [v], sum double
+ *     [v][c], sumsq double [v][c].  Per vertex, for the frames in the order given:
+ *       1. the camera-frame point (x, y, z) by 16(a), 16(b), the vertex widened to float64
+ *       2. the frame is skipped unless z > 0 (NaN skips)
+ *       3. u, v as 16(d) orders them, px = floor(u + o), py = floor(v + o) (rule 17a.4); skipped unless 0 <= px < w and
+ *          0 <= py < h (NaN and infinity skip).  o = 0 for images on dcn_render_depth's grid, 0.5 for the sensor's (rule 17a.5)
+ *       4. mm = depth[py][px]; skipped when mm == 0
+ *       5. e = z * 1000.0 - (double) mm (a product, then a difference); skipped unless -margin_mm <= e <= margin_mm.  Two-sided:
+ *          a vertex behind the surface the view shows is occluded, and one in front of it, projected past a silhouette, would be
+ *          painted with the background
+ *       6. skipped when a mask is given and mask[py][px] == 0
+ *       7. count += 1; per channel in order x = (double) images[py][px][channel], sum += x, sumsq += x * x (a product, then a
+ *          sum).  A NaN descriptor propagates.
+ *     A vertex owns its state and walks its frames in order (no atomics): the state after all frames does not depend on how they
+ *     were split over launches (frames_per_launch, 1 .. 64, < 0: the default 64) or over calls.  One work-item per vertex; no
+ *     host synchronisation.  v >= 0, f >= 1, h, w in 1 .. 16384.
+ * 18b. dcn_mesh_paint_finish: mean float [v][c], variance float [v] and, where colours is not NULL, colours uint8 [v][3].  For a
+ *     vertex with n = count >= min_views (>= 1): mean_c = sum_c / n; var_c = sumsq_c / n - mean_c * mean_c in float64 on the
+ *     unrounded mean (a quotient, a product, a difference), a negative result counts as 0; variance = (((0 + var_0) + var_1) +
+ *     ...) in channel order; each output is rounded to float once.  For any other vertex mean is 0 and variance NaN (the tables'
+ *     NaN convention).  The square root is not taken here.  Colours: for e = 0, 1, 2 with ch = channel_e (in [0, c)) and
+ *     lo, hi device double [c]: t = (mean_ch - lo_ch) / (hi_ch - lo_ch) on the float64 mean, clipped to [0, 1],
+ *     byte = rint(t * 255), ties to even; a NaN t, or hi_ch == lo_ch, gives 0; a vertex with count < min_views gets
+ *     (unseen_red, unseen_green, unseen_blue), each in 0 .. 255.  With uint8 views, lo = 0 and hi = 255 give the rounded mean
+ *     colour.
+ * ===================================================================================================== */
+#define DCN_PAINT_UINT8 0
+#define DCN_PAINT_FLOAT 1
+int dcn_mesh_paint(int v, const float* vertices, const int32_t* valid_vertices, int f, int h, int w, int c, int image_type,
+                   const void* images, const uint16_t* depth, const uint8_t* mask, const float* camera_to_world, double fx,
+                   double fy, double cx, double cy, double pixel_offset, double margin_mm, int frames_per_launch, int32_t* count,
+                   double* sum, double* sumsq, void* stream);
+int dcn_mesh_paint_finish(int v, int c, const int32_t* count, const double* sum, const double* sumsq, int min_views, float* mean,
+                          float* variance, int channel0, int channel1, int channel2, const double* lo, const double* hi,
+                          int unseen_red, int unseen_green, int unseen_blue, uint8_t* colours, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -26,17 +26,27 @@ struct Pinhole {
 // 17a, step 1: the world coordinate of voxel index i on an axis
 __device__ __forceinline__ double voxel_centre(double origin, double s, int i) { return rs::add(origin, rs::mul(s, (double)i)); }
 
-// 17a, steps 2-8 for one voxel centre and one frame: does the frame reach the voxel, and with which q.  cam: the 12 entries of
-// 16(a); depth: the frame's image.
-__device__ __forceinline__ bool observe(const double* cam, const Pinhole& k, double wx, double wy, double wz,
-                                        const uint16_t* __restrict__ depth, int h, int w, int max_mm, double mu, int& q) {
-    const double z = rs::camera_coord(cam + 8, wx, wy, wz);
+// 17a, steps 2-4 for one world point and one frame (also 18a, steps 1-3): its camera-frame depth z and the pixel that holds its
+// projection, pixel = py * w + px; false when the frame does not see the point.  cam: the 12 entries of 16(a).
+__device__ __forceinline__ bool project(const double* cam, const Pinhole& k, double wx, double wy, double wz, int h, int w,
+                                        double& z, int& pixel) {
+    z = rs::camera_coord(cam + 8, wx, wy, wz);
     if (!(z > 0.0)) return false;                                          // (NaN: skipped)
     const double x = rs::camera_coord(cam, wx, wy, wz), y = rs::camera_coord(cam + 4, wx, wy, wz);
     const double pu = floor(rs::add(rs::add(rs::quot(rs::mul(k.fx, x), z), k.cx), k.offset));
     const double pv = floor(rs::add(rs::add(rs::quot(rs::mul(k.fy, y), z), k.cy), k.offset));
     if (!(pu >= 0.0 && pu < (double)w && pv >= 0.0 && pv < (double)h)) return false;   // (NaN, infinity: skipped)
-    const int mm = depth[(size_t)(int)pv * (size_t)w + (size_t)(int)pu];
+    pixel = (int)pv * w + (int)pu;                                         // (h, w <= 16384: below 2^28)
+    return true;
+}
+
+// 17a, steps 2-8 for one voxel centre and one frame: does the frame reach the voxel, and with which q.  depth: the frame's image.
+__device__ __forceinline__ bool observe(const double* cam, const Pinhole& k, double wx, double wy, double wz,
+                                        const uint16_t* __restrict__ depth, int h, int w, int max_mm, double mu, int& q) {
+    double z;
+    int pixel;
+    if (!project(cam, k, wx, wy, wz, h, w, z, pixel)) return false;
+    const int mm = depth[pixel];
     if (mm == 0 || mm > max_mm) return false;
     const double diff = rs::add(rs::quot((double)mm, 1000.0), -z);         // (a + (-b) is a - b, one rounding)
     if (!(diff > -mu)) return false;

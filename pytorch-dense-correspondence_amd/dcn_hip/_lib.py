@@ -278,6 +278,10 @@ SYMBOLS = {
                          + [c_void_p] * 5),
     "dcn_mesh_crop_workspace": (c_size_t, [c_int, c_int64]),
     "dcn_mesh_crop": (c_int, [c_int, c_int64, c_void_p, c_void_p, c_void_p, c_int, c_int] + [c_void_p] * 5),
+    "dcn_mesh_paint": (c_int, [c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int] + [c_void_p] * 4
+                       + [ctypes.c_double] * 6 + [c_int] + [c_void_p] * 4),
+    "dcn_mesh_paint_finish": (c_int, [c_int, c_int] + [c_void_p] * 3 + [c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p,
+                                                                        c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
 }
 
 ERRORS = {-1: "DCN_E_INVALID (bad argument)", -2: "DCN_E_LAUNCH (kernel launch failed)",

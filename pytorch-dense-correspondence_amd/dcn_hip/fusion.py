@@ -11,7 +11,7 @@ CUDA tsdf-fusion binary, marching cubes (doc/data_processing_single_scene.md:42-
 
 The arithmetic is defined in the header (17a-17c): integers and single correctly rounded float64 operations, the same bit for
 bit from run to run.  The surface is extracted by marching tetrahedra, not marching cubes: about twice the triangles.  Colour
-fusion, decimation and the director applications are not provided."""
+fusion is ``dcn_hip.paint``'s; decimation and the director applications are not provided."""
 import numpy as np
 import torch
 
